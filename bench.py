@@ -10,10 +10,15 @@ leapfrog steps, accept, state update, and the state of every chain RECORDED as t
 burn-in, eeyore/samplers/serial_sampler.py:35-52, eeyore/chains/chain_list.py:64-67), BASELINE.json configs[2]:
 4096 chains per GPU, MLP(4-32-32-3; sigmoid, sigmoid, None), CE-sum, prior N(0, sqrt 3), N = 150 rows, fp32.
 Steps are issued as `HMC.run` issues them: whole launches of 25 iterations (ey_hmc_run writing samples / targets /
-accept flags into the chain buffer); --steps is rounded UP to whole launches and the line says so.
-Chains shard over ranks with no collective in the step (weak scaling: 4096 chains per GPU, configs[3] at N = 8);
-when N > 1 the per-parameter R-hat and ESS summaries are combined over RCCL once at the end of the timed region.
+accept flags into the chain buffer), then one launch of the remainder: exactly --steps iterations are timed.
+Chains shard over ranks with no collective in the step (weak scaling: 4096 chains per GPU, configs[3] at N = 8).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the secondary measurements and checks
+behind it: the R-hat and ESS summaries (combined over RCCL when N > 1), the dominant kernel timed alone (roofline) and in
+the other form of its products, the same workload through samplers.HMC.run, BASELINE configs[4]'s share of one GPU and
+the CPU baselines.  --dump-outputs DIR writes what the last timed step computed (rank 0's chains) as DIR/<name>.npy; the
+inputs are seeded, so runs with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +58,26 @@ def kernel_source_hash():
         with open(os.path.join(ROOT, "eeyore_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much (the default run's outputs are 43 MB)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `arrays` (name -> device tensor, chains along the first axis) as path/<name>.npy, float64 kept and
+    everything else as float32.  When they would hold more than `limit` bytes, the same fixed, seeded sample of chains is
+    written from every array, and their numbers as chain_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in host.items()}
+    C = next(iter(host.values())).shape[0]
+    per_chain = sum(v.nbytes // C for v in host.values())
+    if C * per_chain > limit:
+        rows = np.sort(np.random.default_rng(0).choice(C, limit // (per_chain + 8), replace=False))
+        host = {k: v[rows] for k, v in host.items()}
+        host["chain_index"] = rows.astype(np.float64)
+    for k, v in host.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(v))
 
 
 def cpu_reference_faithful(x, y, sigma, budget_s=8.0):
@@ -344,13 +369,18 @@ def config5_share(dev, chains=4096, iters=3, burnin=20, step=0.024):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed HMC iterations of every chain (exactly this many)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--chains-per-gpu", type=int, default=CHAINS_PER_GPU)
     ap.add_argument("--iters-per-launch", type=int, default=25,
                     help="HMC iterations (bench steps) per kernel launch: ey_hmc_run, as HMC.run issues them; 1 = ey_hmc_step")
-    ap.add_argument("--min-launches", type=int, default=5,
-                    help="the timed region holds at least this many launches (of --iters-per-launch iterations each)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, the secondary measurements and checks: R-hat and ESS summaries, the dominant "
+                         "kernel timed alone (roofline) and in the other form of its products, the same workload through "
+                         "samplers.HMC.run, BASELINE configs[4]'s share of one GPU, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed (states, log-targets, gradients, "
+                         "accept flags) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-record", action="store_true",
                     help="do not record the chains in the timed region (round 3's figure: the kernel without the sample store)")
@@ -366,6 +396,8 @@ def main():
                     help="launcher / rendezvous / collectives only (no GPU needed, prints value null): the CPU-side test of "
                          "the multi-rank plumbing; never a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
 
@@ -405,11 +437,9 @@ def main():
     if args.force_generic:
         ipl = 1  # the generic family replays attached moments from recorded samples; keep its one-step form
 
-    # --steps rounded up to whole launches: the timed region is what HMC.run issues after burn-in -- and
-    # to at least --min-launches of them: one 21 ms launch is a single sample of a quantity that moves by
-    # +-10 % from launch to launch; `steps` in the line is what was timed, `config.steps_requested` what was asked for
-    n_launches = max((args.steps + ipl - 1) // ipl, 1 if args.force_generic else max(1, args.min_launches))
-    steps_timed = n_launches * ipl
+    # the timed region is exactly --steps iterations, issued as HMC.run issues them after burn-in: whole launches of `ipl`
+    # iterations, then one launch of the remainder; `config.launch_ms_*` carry the spread of the timed launches
+    steps_timed = args.steps
     # the chain buffer of the timed region, [iterations, C, P] + targets + accept flags, as ChainBuffer holds a run
     # (200 steps x 4096 x 1315 floats = 4.3 GB), and one launch's worth for the untimed launches around it
     record = not args.no_record and not args.force_generic
@@ -419,11 +449,13 @@ def main():
 
     launch_events = None  # a list while the timed region runs: one event in front of every launch (and one behind the last)
 
-    def steps(it, n, rec_at=None):
+    def steps(it, n, rec_at=None, state=None):
         """n bench steps = n HMC iterations of every chain, starting at iteration number `it`: whole launches of `ipl`
         iterations (what HMC.run does after burn-in), then the remainder.  Every launch records the chains' states,
         log-targets and accept flags: the timed region into consecutive blocks of the chain buffer starting at `rec_at`,
-        the untimed launches into its first block."""
+        the untimed launches into its first block.  `state`: other (theta, target, grad) tensors to advance than the
+        chains'."""
+        th, tg, gr = (theta, target, grad) if state is None else state
         done = 0
         while done < n:
             k = min(ipl, n - done)
@@ -436,10 +468,10 @@ def main():
                 r0 = 0 if rec_at is None else rec_at + done
                 kw = dict(samples=rec["s"][r0:r0 + k], targets=rec["t"][r0:r0 + k], accepted_rec=rec["a"][r0:r0 + k])
             if k == 1 and not record:
-                plan.hmc_step(theta, target, grad, STEP_SIZE, L_STEPS, seed=seed, it=it + done,
+                plan.hmc_step(th, tg, gr, STEP_SIZE, L_STEPS, seed=seed, it=it + done,
                               chain_offset=chain_offset, flags=flags, out=out)
             else:
-                plan.hmc_run(theta, target, grad, STEP_SIZE, L_STEPS, k, seed=seed, it=it + done,
+                plan.hmc_run(th, tg, gr, STEP_SIZE, L_STEPS, k, seed=seed, it=it + done,
                              chain_offset=chain_offset, flags=flags, out=out, **kw)
             done += k
 
@@ -447,8 +479,14 @@ def main():
     stats.attach(plan)
     it = 1
     steps(it, args.warmup); it += args.warmup
-    stats.summary()  # warms the torch elementwise kernels (and the RCCL communicator) of the summary below
+    if args.full:
+        stats.summary()  # warms the torch elementwise kernels (and the RCCL communicator) of the summary below
     warm_stats, stats = stats, ChainStats(C, P, dev)  # the timed region's accumulators, allocated and zeroed now
+    # The settling launches below advance a copy of the chains, with iteration numbers past the timed region's: their
+    # number follows the clock, and the timed steps must start from the same state and draw the same numbers in every run
+    # with the same arguments (--dump-outputs: two builds compared output for output).
+    it_timed, it = it, it + steps_timed
+    settle = (theta.clone(), target.clone(), grad.clone())
     # Clock settling, independent of --warmup: the device drops its clocks whenever it idles for a few milliseconds
     # (the allocations and host work above) and ramps them over the first hundreds of milliseconds of load, so a 20-step
     # run (23 ms) would be timed on the ramp.  Untimed launches, the same as the timed ones, queued without a gap; the
@@ -461,7 +499,7 @@ def main():
         dist.barrier()
     t_pre = time.perf_counter()
     for _ in range(4):
-        steps(it, ipl); it += ipl
+        steps(it, ipl, state=settle); it += ipl
     torch.cuda.synchronize()
     batch_s = max(time.perf_counter() - t_pre, 1e-4)
     n_batches = max(0, int(np.ceil(args.prewarm_seconds / batch_s)) - 1)
@@ -470,7 +508,7 @@ def main():
         dist.all_reduce(nb, op=dist.ReduceOp.MAX)
         n_batches = int(nb.item())
     for _ in range(4 * n_batches):
-        steps(it, ipl); it += ipl
+        steps(it, ipl, state=settle); it += ipl
     torch.cuda.synchronize()
     stats.attach(plan)  # host-side only: no device work between the warm launches and the timed ones
     if world > 1:
@@ -478,7 +516,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     launch_events = []
-    steps(it, steps_timed, rec_at=0); it += steps_timed
+    steps(it_timed, steps_timed, rec_at=0)
     ev_end = torch.cuda.Event(enable_timing=True)
     ev_end.record()
     timed_events, launch_events = launch_events + [ev_end], None
@@ -487,17 +525,23 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    del settle
+    if args.dump_outputs and rank == 0:
+        # what ey_hmc_run hands back (out's rate / h_cur / h_prop are written by the one-step entry point only)
+        dump_outputs(args.dump_outputs, dict(theta=theta, target=target, grad=grad, accepted=out["accepted"]))
     # the gather of chain statistics (R-hat summary; one RCCL all-reduce of [3, P] partial sums when world > 1) happens
     # once per run, not per step: timed on its own and reported in config
-    t1 = time.perf_counter()
-    summ = stats.summary() if steps_timed > 1 else None
-    torch.cuda.synchronize()
-    summary_ms = 1e3 * (time.perf_counter() - t1)
+    summ = summary_ms = None
+    if args.full:
+        t1 = time.perf_counter()
+        summ = stats.summary() if steps_timed > 1 else None
+        torch.cuda.synchronize()
+        summary_ms = 1e3 * (time.perf_counter() - t1)
     # ... and the effective sample sizes (configs[3]: "gather of R-hat/ESS"): every (chain, parameter) series of the
     # recorded buffer through ey_inse_univariate on this rank, then min / mean / total per parameter over all ranks
     # (two small all-reduces, distributed.reduce_ess); also outside the step clock, timed on its own
     ess = None
-    if record and steps_timed >= 20:  # (the driver's --steps 20 becomes one launch of 25: a short series, but the gather runs)
+    if args.full and record and steps_timed >= 20:
         from eeyore_amd.stats import batched
         t2 = time.perf_counter()
         ess = reduce_ess(batched.ess(rec["s"][:steps_timed]))
@@ -522,11 +566,11 @@ def main():
         stats.attach(plan)
         return float(np.mean([a.elapsed_time(b) for a, b in evs]))
 
-    kern_ms = launch_ms()
+    kern_ms = launch_ms() if args.full else None
     # the same launches with the other form of the kernel's 32x32x32 products (EY_OPT_F32_PRODUCTS), for the record
     products = plan.f32_products if plan.kernel == "mfma32" else None
     other = None
-    if products is not None and not args.force_generic and not args.no_compare:
+    if args.full and products is not None and not args.force_generic and not args.no_compare:
         plan.f32_products = "exact" if products == "bf16x3" else "bf16x3"
         steps(it, ipl); it += ipl
         other = (plan.f32_products, launch_ms())
@@ -534,7 +578,7 @@ def main():
 
     # the same workload through samplers.HMC.run -> ChainBuffer (the path a reference script takes), same start, own clock
     via_sampler = None
-    if record and not args.no_sampler_run:
+    if args.full and record and not args.no_sampler_run:
         theta0 = 0.1 * plan.philox_normal(C, seed=0, it=0, chain_offset=chain_offset)
         s_elapsed, s_acc = through_sampler_run(xs, ys, sigma, theta0, dev, steps_timed, ipl, seed, chain_offset, world, gloo)
         via_sampler = (s_elapsed, s_acc)
@@ -544,7 +588,6 @@ def main():
         f_step = flops_per_leapfrog_step(DIMS, N_ROWS)
         total_chains = C * world
         value = total_chains * L_STEPS * steps_timed / elapsed
-        achieved_tflops = f_step * L_STEPS * C * ipl / (kern_ms * 1e-3) / 1e12
         line = {
             "metric": "leapfrog-steps/sec x chains, HMC MLP(4-32-32-3)",
             "value": value,
@@ -567,21 +610,25 @@ def main():
                 "f32_products": None if args.force_generic else products,
                 "gradient_evaluations_per_iteration": L_STEPS, "iterations_per_launch": ipl,
                 "steps_requested": args.steps,
-                "steps_note": (f"--steps {args.steps} rounded up to {steps_timed} = {steps_timed // ipl} whole launch(es) of {ipl} "
-                               f"iterations, as HMC.run issues them (at least --min-launches {args.min_launches}); `steps` and "
-                               f"`ms_per_step` are those of the timed region") if steps_timed != args.steps else "whole launches",
-                "launches_timed": steps_timed // ipl,
+                "steps_note": "whole launches" if steps_timed % ipl == 0 else (
+                    f"{steps_timed // ipl} whole launch(es) of {ipl} iterations, then one of {steps_timed % ipl}"),
+                "launches_timed": len(launch_gaps),
                 "launch_ms_min": round(min(launch_gaps), 4), "launch_ms_median": round(float(np.median(launch_gaps)), 4),
                 "launch_ms_max": round(max(launch_gaps), 4),
                 "launch_ms_note": "start-to-start of consecutive launches inside the timed region (HIP events on the launch stream)",
                 "recorded_in_timed_region": ("samples [steps, C, P], targets [steps, C], accepted [steps, C] (the chain buffer "
                                              "HMC.run fills after burn-in)") if record else None,
+            },
+        }
+        if args.full:
+            achieved_tflops = f_step * L_STEPS * C * ipl / (kern_ms * 1e-3) / 1e12
+            line["config"].update({
                 "stats_summary_ms": round(summary_ms, 3),
                 "value_including_stats_summary": total_chains * L_STEPS * steps_timed / (elapsed + 1e-3 * summary_ms),
                 "acceptance": None if summ is None else round(summ["acceptance"], 4),
                 "rhat_max": None if summ is None else float(summ["rhat"].max().item()),
-            },
-            "roofline": {
+            })
+            line["roofline"] = {
                 "bound": "mfma", "achieved": achieved_tflops, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                 "frac": achieved_tflops / PEAK_F32_MFMA_TFLOPS, "traffic": None,
                 "kernel_ms": kern_ms, "leapfrog_steps_per_launch": C * L_STEPS * ipl,
@@ -590,15 +637,14 @@ def main():
                 # what the matrix pipes sustain alone at the socket's power limit (tools/mfma_power_probe.hip, operands whose bits
                 # change; profiles/r05_mfma_power_probe.txt, r05_clock_power.txt: this kernel runs at 1 360 W and 2.36 GHz)
                 "sustained_at_power_limit": {"f32_mfma_tflops": 139.5, "bf16_mfma_tflops": [1731.7, 1814.6]},
-            },
-        }
+            }
         if ess is not None:
             line["config"]["ess"] = {"summary_ms": round(ess_ms, 3), "min_over_chains_and_parameters": float(ess["min"].min().item()),
                                      "mean": float(ess["mean"].mean().item()), "total_per_parameter_mean": float(ess["total"].mean().item()),
                                      "num_chains": ess["num_chains"], "series_without_enough_samples": ess["not_enough"],
                                      "from": f"{steps_timed} recorded iterations of every chain (ey_inse_univariate), combined "
                                              f"over ranks by distributed.reduce_ess"}
-        if world == 1 and not args.no_config5 and not args.force_generic and not args.no_compare:
+        if args.full and world == 1 and not args.no_config5 and not args.force_generic and not args.no_compare:
             try:  # a secondary figure: never in the way of the headline line
                 line["config"]["secondary"] = {"config5_share_one_gpu": config5_share(dev)}
             except Exception as e:  # noqa: BLE001
@@ -617,7 +663,7 @@ def main():
                 other[0]: {"kernel_ms": other[1], "tflops": o_tflops, "frac": o_tflops / PEAK_F32_MFMA_TFLOPS,
                            "leapfrog_steps_per_sec_x_chains": C * L_STEPS * ipl / (other[1] * 1e-3)},
             }
-        if products == "bf16x3" and not args.force_generic:
+        if args.full and products == "bf16x3" and not args.force_generic:
             # The f32-equivalent fraction above prices the ALGORITHMIC f32 flops against the f32 matrix peak.  Beside it, how
             # much of the kernel's time each matrix pipe is issuing (per SIMD, at the nominal 2.4 GHz): per 32-row tile 36
             # v_mfma_f32_32x32x16_bf16 (32 cycles each), 2 v_mfma_f32_32x32x2_f32 (64) and 60 v_mfma_f32_4x4x1_16b_f32 (8.4)
@@ -638,7 +684,7 @@ def main():
         # HBM traffic of the dominant kernel from the committed PMC passes (tools/pmc_passes.sh; separate --pmc runs,
         # FETCH_SIZE doubled as MI355X_MICROARCH.md's HBM section prescribes for gfx950); bench.py cannot profile itself
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc) and not args.force_generic and C == CHAINS_PER_GPU:
+        if args.full and os.path.exists(pmc) and not args.force_generic and C == CHAINS_PER_GPU:
             with open(pmc) as f:
                 pm = json.load(f)
             # only counters collected on THIS kernel source count (tools/pmc_passes.sh records its hash)
@@ -654,7 +700,7 @@ def main():
                     "survey_8d_bytes_per_launch": (2 * P + P) * 4 * C * ipl,
                     "note": "SURVEY 8(d): (2 P + P_store) * 4 / L bytes per leapfrog step per chain = theta and gradient in, the "
                             "recorded sample out, per iteration; an accepted draw also writes theta and the gradient back"}
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure (the other ranks would wait for it)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure (the other ranks would wait for it)
             # BASELINE.md section 3 item 3, "generous CPU": one chain per hardware thread on ALL threads this process may
             # use; beside it the 16 threads that are a one-GPU box's share of the host, and the reference-faithful path
             # (a box may show all 256 threads of its host and schedule this job on a share of them -- measured on the pool:

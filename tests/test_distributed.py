@@ -277,6 +277,33 @@ def test_bench_launcher_reports_a_failed_rank():
     assert rc != 0
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_within_its_limit(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one DIR/<name>.npy per array, float64 kept and the rest as float32; above the
+    size limit the same seeded sample of chains from every array, with their numbers, and the same sample in every run."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = dict(theta=torch.tensor(rng.standard_normal((40, 6)), dtype=torch.float32),
+                  target=torch.tensor(rng.standard_normal(40)), accepted=torch.tensor(rng.random(40) < 0.5))
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert sorted(os.listdir(tmp_path / "all")) == ["accepted.npy", "target.npy", "theta.npy"]
+    assert got["theta"].dtype == np.float32 and got["target"].dtype == np.float64 and got["accepted"].dtype == np.float32
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(got[k], v.numpy().astype(got[k].dtype))
+    limit = 10 * (6 * 4 + 8 + 4)  # ten chains' worth, before the index
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["accepted.npy", "chain_index.npy", "target.npy", "theta.npy"]
+    assert sum(np.load(tmp_path / "s1" / f).nbytes for f in files) <= limit
+    rows = np.load(tmp_path / "s1" / "chain_index.npy")
+    assert rows.dtype == np.float64 and len(rows) >= 5 and (np.diff(rows) > 0).all() and rows[-1] < 40
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), v.numpy()[rows.astype(int)].astype(got[k].dtype))
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "s2" / f), np.load(tmp_path / "s1" / f))
+
+
 # ----------------------------------------------------------------------------------- eight ranks, uneven shards (gloo)
 # BASELINE configs[3] and [4] run on eight GPUs, and no 8-GPU node is available to this suite: these tests take the
 # whole multi-rank path -- chain statistics, sharded multi_rhat, the tempering exchange, bench.py's own launcher --
