@@ -91,6 +91,10 @@ struct ey_plan {
   hipEvent_t xpre_event = nullptr;   // recorded behind the split on the stream that ran it: a consumer on another stream waits for it
   hipStream_t xpre_stream = nullptr;
   uint64_t data_version = 0, xpre_version = ~0ull;  // ey_plan_set_data counts; the images remember which batch they hold
+  // the fused narrow- and mid-size kernels (ey_mid.hip): k_mid32's parameter -> LDS table [P], built on first use, and
+  // whether their LDS limit has been raised
+  int* d_mid32_tab = nullptr;
+  bool mid32_attr = false, mid_attr = false;
 };
 
 // The diagnostic switches of the plan a C-ABI call is serving, for the dispatch code below the entry points (thread-local:
@@ -156,8 +160,7 @@ int ey_stats_update_run(const void* samples, const void* accepted_rec, int n_it,
 bool ey_mid_supports(const ey_plan* pl);
 int ey_mid_eval(ey_plan* pl, const float* theta, const float* temp, int C, float* lik_o, float* grad, hipStream_t s);
 bool ey_mid32_supports(const ey_plan* pl);  // narrow deeper models: every hidden width <= 32, up to three hidden layers, d_0 <= 64
-int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, float* lik_o, float* grad, void* scratch,
-                  hipStream_t s);
+int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, float* lik_o, float* grad, hipStream_t s);
 
 // generic kernels (ey_generic.hip)
 int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,

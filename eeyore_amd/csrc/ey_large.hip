@@ -2265,6 +2265,8 @@ void ey_large_free(ey_plan* pl) {
   pl->xpre_bytes = 0;
   if (pl->xpre_event) (void)hipEventDestroy(pl->xpre_event);
   pl->xpre_event = nullptr;
+  (void)hipFree(pl->d_mid32_tab);
+  pl->d_mid32_tab = nullptr;
 }
 
 // The data matrix x [N, d0] as the first layer's forward product takes it in the bf16x3 form (its A operand: rows n, k =
@@ -2392,7 +2394,7 @@ static int eval_chunk(ey_plan* pl, const T* theta, const T* temp, int C, T* lik_
       mid = true;
     } else if (grad && !rows_o && !lf && !EY_VBIT(14) && ey_mid32_supports(pl)) {
       // narrow deeper models (every hidden width <= 32): one wave per row tile, no barrier inside a chain's rounds
-      if ((rc = ey_mid32_eval(pl, (const float*)theta, (const float*)temp, C, (float*)lik_tmp, (float*)grad, (void*)ws, s))) return rc;
+      if ((rc = ey_mid32_eval(pl, (const float*)theta, (const float*)temp, C, (float*)lik_tmp, (float*)grad, s))) return rc;
       mid = true;
     }
   }

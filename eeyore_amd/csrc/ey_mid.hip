@@ -23,6 +23,7 @@
 // eeyore/stats/loss.py:1-11, the gradient eeyore/models/log_target_model.py:15-23 (autograd there).
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 #include "ey_common.h"
 
@@ -41,7 +42,7 @@ struct MidArgs {
   const float* temp;    // [C] or null
   float* lik_o;         // [C]: the untempered log-likelihood
   float* grad;          // [C, P]: gradient of the tempered log-target
-  const int* tab;       // k_mid32: [P] where each parameter goes in the LDS images (k_mid32_table)
+  const int* tab;       // k_mid32: [P] where each parameter goes in the LDS images (the plan's, mid32_table)
   int C, N, P, nl, lik, prior_uniform;
   float mu0, iv0;
   int dims[MID_NL + 1], woff[MID_NL], boff[MID_NL], act[MID_NL];
@@ -756,22 +757,9 @@ __device__ __forceinline__ void mid_wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS operations of one wave execute in order: a compiler fence
   __builtin_amdgcn_wave_barrier();
 }
-// where in the LDS images each parameter of theta goes (k_mid32 stages a chain with all its loads in flight at once: taken
-// row by row every element waited out its own trip to memory, a dozen serial round trips per chain)
-__global__ void k_mid32_table(MidArgs A, int* __restrict__ tab) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= A.P) return;
-  int dst = -1;
-  for (int l = 0; l < A.nl; ++l) {
-    const int din = A.dims[l], dout = A.dims[l + 1];
-    if (e >= A.woff[l] && e < A.woff[l] + din * dout) {
-      const int f = (e - A.woff[l]) / din, k = (e - A.woff[l]) - f * din;
-      dst = A.w_at[l] + f * A.ldw[l] + k;
-    }
-    if (A.boff[l] >= 0 && e >= A.boff[l] && e < A.boff[l] + dout) dst = A.b_at[l] + (e - A.boff[l]);
-  }
-  tab[e] = dst;
-}
+// k_mid32 stages a chain with all its loads in flight at once, each parameter's LDS destination read from the plan's table
+// (A.tab, mid32_table below): taken row by row every element waited out its own trip to memory, a dozen serial round trips
+// per chain
 #define MID32_SPT 10  // parameters per thread at most (P <= 4720 for 64 inputs, three hidden layers of 32, 16 outputs)
 template <int NB0>  // 32-wide input blocks of the first layer: 1 (d_0 <= 32) or 2
 __global__ void __launch_bounds__(512, 2) k_mid32(MidArgs A_) {
@@ -1193,22 +1181,49 @@ static void mid_fill(ey_plan* pl, MidArgs& a, const float* theta, const float* t
   for (int l = 0; l <= m.nl; ++l) a.dims[l] = m.dims[l];
   for (int l = 0; l < m.nl; ++l) { a.woff[l] = m.woff[l]; a.boff[l] = m.boff[l]; a.act[l] = m.act[l]; }
 }
-int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, float* lik_o, float* grad, void* scratch,
-                  hipStream_t s) {
+// where each parameter goes in k_mid32's LDS images (A.tab): it depends on the weight and bias carve alone, which mid32_plan
+// lays out before anything that depends on the batch, so each plan builds it once, on the host, into a buffer of its own
+static int mid32_table(ey_plan* pl, const MidArgs& a) {
+  if (pl->d_mid32_tab) return EY_OK;
+  std::vector<int> tab(a.P);
+  for (int e = 0; e < a.P; ++e) {
+    int dst = -1;
+    for (int l = 0; l < a.nl; ++l) {
+      const int din = a.dims[l], dout = a.dims[l + 1];
+      if (e >= a.woff[l] && e < a.woff[l] + din * dout) {
+        const int f = (e - a.woff[l]) / din, k = (e - a.woff[l]) - f * din;
+        dst = a.w_at[l] + f * a.ldw[l] + k;
+      }
+      if (a.boff[l] >= 0 && e >= a.boff[l] && e < a.boff[l] + dout) dst = a.b_at[l] + (e - a.boff[l]);
+    }
+    tab[e] = dst;
+  }
+  int* d = nullptr;
+  EY_HIP(hipMalloc(&d, (size_t)a.P * sizeof(int)));
+  if (hipMemcpy(d, tab.data(), (size_t)a.P * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    EY_FAIL(EY_ERR_HIP, "ey_mid32_eval: copying the parameter table failed");
+  }
+  pl->d_mid32_tab = d;
+  return EY_OK;
+}
+int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, float* lik_o, float* grad, hipStream_t s) {
   MidArgs a = {};
   if (!mid32_plan(pl->m, a)) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_mid32_eval: model not served by the fused narrow-model kernel");
   mid_fill(pl, a, theta, temp, C, lik_o, grad);
-  a.tab = (const int*)scratch;  // (P integers of the caller's activation workspace, which this path does not use otherwise)
-  hipLaunchKernelGGL(k_mid32_table, dim3((a.P + 255) / 256), dim3(256), 0, s, a, (int*)scratch);
+  if (int rc = mid32_table(pl, a)) return rc;
+  a.tab = pl->d_mid32_tab;
   const size_t bytes = (size_t)a.total_floats * sizeof(float);
   const unsigned grid = (unsigned)std::min<int64_t>(C, pl->n_cu > 0 ? pl->n_cu : 256);
-  if (pl->m.dims[0] > 32) {
-    EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid32<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_mid32<2>, dim3(grid), dim3(512), bytes, s, a);
-  } else {
+  if (!pl->mid32_attr) {  // (once per plan: the limit belongs to the kernels, not to this launch)
     EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid32<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_mid32<1>, dim3(grid), dim3(512), bytes, s, a);
+    EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid32<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    pl->mid32_attr = true;
   }
+  if (pl->m.dims[0] > 32)
+    hipLaunchKernelGGL(k_mid32<2>, dim3(grid), dim3(512), bytes, s, a);
+  else
+    hipLaunchKernelGGL(k_mid32<1>, dim3(grid), dim3(512), bytes, s, a);
   EY_HIP(hipGetLastError());
   return EY_OK;
 }
@@ -1232,13 +1247,15 @@ int ey_mid_eval(ey_plan* pl, const float* theta, const float* temp, int C, float
   for (int l = 0; l < m.nl; ++l) { a.woff[l] = m.woff[l]; a.boff[l] = m.boff[l]; a.act[l] = m.act[l]; }
   const size_t bytes = (size_t)a.total_floats * sizeof(float);
   const unsigned grid = (unsigned)std::min<int64_t>(C, pl->n_cu > 0 ? pl->n_cu : 256);
-  if (m.dims[0] > 32) {
-    EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_mid<true>, dim3(grid), dim3(512), bytes, s, a);
-  } else {
+  if (!pl->mid_attr) {
     EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_mid<false>, dim3(grid), dim3(512), bytes, s, a);
+    EY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    pl->mid_attr = true;
   }
+  if (m.dims[0] > 32)
+    hipLaunchKernelGGL(k_mid<true>, dim3(grid), dim3(512), bytes, s, a);
+  else
+    hipLaunchKernelGGL(k_mid<false>, dim3(grid), dim3(512), bytes, s, a);
   EY_HIP(hipGetLastError());
   return EY_OK;
 }
