@@ -641,6 +641,44 @@ int ey_mh_run(ey_plan* pl, void* theta, void* target, const void* scale, const v
                  stream, &run, "ey_mh_run");
 }
 
+// RAM runs on k_ram (ey_generic.hip) for every model: the fused families have no factor to adapt
+static int ram_impl(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                    void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
+  int rc = check_ready(pl, C, who);
+  if (rc) return rc < 0 ? rc : EY_OK;
+  EyVariantScope vs(pl);
+  if (!theta || !target || !chol || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
+  if (n == 0) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the adaptation index n must be >= 1");
+  if (!(a > 0.0 && a < 1.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the target acceptance a must lie in (0, 1)");
+  if (!std::isfinite(g)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the decay exponent g must be finite");
+  if (C == 0) return EY_OK;
+  if ((rc = moments_check(pl, C, who))) return rc;
+  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
+  EY_HIP(hipSetDevice(pl->device));
+  rc = ey_generic_ram(pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted, log_rate,
+                      (hipStream_t)stream, run);
+  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+}
+
+int ey_ram_step(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                uint32_t flags, void* accepted, void* log_rate, void* stream) {
+  (void)flags;
+  return ram_impl(pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted, log_rate, stream,
+                  nullptr, "ey_ram_step");
+}
+
+int ey_ram_run(ey_plan* pl, void* theta, void* target, void* chol, double a, double g, uint64_t n, const void* temp,
+               int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
+               void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
+  (void)flags;
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  return ram_impl(pl, theta, target, chol, nullptr, nullptr, a, g, n, temp, C, seed, iter, chain_offset, accepted,
+                  nullptr, stream, &run, "ey_ram_run");
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------- small kernels

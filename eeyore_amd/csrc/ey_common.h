@@ -178,6 +178,11 @@ int ey_generic_mala(ey_plan* pl, void* theta, void* target, void* grad, const vo
 int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
                   const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
                   void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+// robust adaptive Metropolis (k_ram): every model whose factor fits beside the evaluation image, whatever plan.kernel says
+size_t ey_generic_ram_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
+int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                   uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                   void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
 // layerwise batched-GEMM kernels for large models, f32 (ey_large.hip)
 bool ey_large_needed(const ey_plan* pl, int nvec = 3);  // true when the generic kernels cannot hold the model in LDS

@@ -1077,3 +1077,184 @@ int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const v
   return EY_TINY_DISPATCH(launch_mh, pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset,
                                                 accepted, log_rate, s, run);
 }
+
+// ----------------------------------------------------------------------------------------------- robust adaptive Metropolis
+// RAM.draw (eeyore/samplers/ram.py:38-70; Vihola 2012): propose theta + S z with the chain's lower-triangular factor S,
+// accept as MH does, then ALWAYS adapt  S <- chol(S (I + beta w w^T) S^T),  w = z / |z|,  beta = h (alpha - a),
+// h = min(1, P n^-g).  The re-factorisation has a closed form S' = S L_w, L_w the Cholesky factor of I + beta w w^T:
+//   t_{-1} = 1,  t_k = 1 + beta sum_{j<=k} w_j^2,  d_k = sqrt(t_k / t_{k-1}),  g_k = beta w_k / sqrt(t_{k-1} t_k)
+//   S'[i,k] = d_k S[i,k] + g_k sum_{k<j<=i} S[i,j] w_j                                               (i >= k)
+// so every row of S' is a backward sweep over its own row of S with one running sum of OLD values; only the per-column
+// scalars d_k, g_k are shared.  t_k >= 1 - a > 0 for 0 < a < 1: the update cannot break down.
+// One wave per chain, lane <-> row (rows lane and lane + 64: P <= 128).  The factor stays in LDS for the whole launch,
+// packed lower triangle, column-major: (i, j) at j P - j (j - 1) / 2 + (i - j) -- both sweeps walk a column at
+// consecutive addresses.  Global state: dense [C, P, P] row-major (what torch.linalg.cholesky returns); only j <= i is
+// read or written.  No row-wave form: the kernel is one wave per chain whatever plan.row_waves says.
+#define RAM_MAX_P 128
+__host__ __device__ static inline int ram_col(int j, int P) { return j * P - (j * (j - 1)) / 2; }
+__host__ __device__ static size_t ram_extra_bytes(int P, size_t esz) {
+  const size_t packed = ((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3, Ppad = (P + 3) & ~3;
+  return esz * (packed + 3 * Ppad + WAVE);  // factor, w, d, g, and a slot per lane for the stores of rows above a column
+}
+
+template <typename T, class TINY>
+__global__ void __launch_bounds__(WAVE) k_ram(EyModel m, T* theta, T* target, T* chol, const T* z_in, const T* u_in,
+                                              double a, double g, uint64_t n0, const T* temp, uint64_t seed,
+                                              uint64_t iter0, uint64_t chain_offset, unsigned char* accepted,
+                                              T* log_rate_o, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, 2);
+  const int P = m.P;
+  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 2, sizeof(T)));
+  const int Ppad = (P + 3) & ~3;
+  T* w = S + (((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3);
+  T* dk = w + Ppad;
+  T* gk = dk + Ppad;
+  T* junk = gk + Ppad;
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  T* Sg = chol + c * (int64_t)P * P;
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Sg[(int64_t)i * P + j];
+  T t_state = target[c];
+  for (int it = 0; it < run.n_iters; ++it) {
+    const uint64_t iter = iter0 + (uint64_t)it;
+    // ---- z ~ N(0, I) (ram.py:44), then the proposal theta + S z (:45): a column sweep, one running sum per row
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    if (!z_in) fill_normals<T>(w, rn, P);
+    else {
+      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
+      __syncthreads();
+    }
+    T acc[2] = {T(0), T(0)};
+    for (int j = 0; j < P; ++j) {
+      const T zj = w[j];
+      const T* col = S + ram_col(j, P) - j;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int i = lane + r * WAVE;
+        const bool on = i >= j && i < P;
+        const T s = col[on ? i : j];
+        acc[r] += (on ? s : T(0)) * zj;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      if (i < P) l.th[i] = theta[c * P + i] + acc[r];
+    }
+    __syncthreads();
+    const T tv = eval_target<T, false, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
+    const T log_rate = tv - t_state;  // ram.py:48
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    const T u = u_in ? u_in[c] : ey_rng_uniform<T>(ru);
+    const bool acc_ = Num<T>::log(u) < log_rate;  // :50
+    if (acc_) {
+      t_state = tv;
+      for (int i = lane; i < P; i += WAVE) theta[c * P + i] = l.th[i];
+    }
+    if (run.samples) {
+      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
+      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? l.th[i] : theta[c * P + i];
+    }
+    if (lane == 0) {
+      if (acc_) target[c] = tv;
+      accepted[c] = acc_ ? 1 : 0;
+      if (log_rate_o) log_rate_o[c] = log_rate;
+      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
+      if (run.accept_count && acc_) run.accept_count[c] += 1;
+    }
+    // ---- adaptation (:59-63), accepted or not.  alpha = min(1, exp(log_rate)) as Python's min takes it: NaN -> 1.
+    const T e = Num<T>::exp(log_rate);
+    const T alpha = e < T(1) ? e : T(1);
+    const double h = fmin(1.0, (double)P * pow((double)(n0 + (uint64_t)it), -g));
+    const T beta = (T)(h * ((double)alpha - a));
+    T zz = T(0);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      const T zi = w[i < P ? i : 0];
+      zz += (i < P ? zi : T(0)) * zi;
+    }
+    const T nrm = Num<T>::sqrt(wave_sum(zz));
+    __syncthreads();  // every lane has read z
+    for (int i = lane; i < P; i += WAVE) w[i] = w[i] / nrm;
+    __syncthreads();
+    // d_k, g_k: lane k sums w_j^2 over j < k in the order j = 0, 1, ... (lane k - 1 adds the same terms in the same order)
+    T pre[2] = {T(0), T(0)};
+    for (int j = 0; j < P; ++j) {
+      const T wj = w[j];
+      const T q = wj * wj;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) pre[r] += (j < lane + r * WAVE) ? q : T(0);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int k = lane + r * WAVE;
+      const T wk = w[k < P ? k : 0];
+      const T t0 = T(1) + beta * pre[r];
+      const T t1 = T(1) + beta * (pre[r] + wk * wk);
+      if (k < P) {
+        dk[k] = Num<T>::sqrt(t1 / t0);
+        gk[k] = beta * wk / Num<T>::sqrt(t0 * t1);
+      }
+    }
+    __syncthreads();
+    // backward column sweep: row i keeps sum_{j>k} S_old[i,j] w_j; a lane whose row lies above column k stores into its
+    // own slot of `junk` (no store behind a per-lane branch while the running sums are live)
+    T run_s[2] = {T(0), T(0)};
+    for (int k = P - 1; k >= 0; --k) {
+      const T d = dk[k], gm = gk[k], wk = w[k];
+      T* col = S + ram_col(k, P) - k;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int i = lane + r * WAVE;
+        const bool on = i >= k && i < P;
+        const T s = col[on ? i : k];
+        const T so = on ? s : T(0);
+        const T nv = d * so + gm * run_s[r];
+        run_s[r] += so * wk;
+        *(on ? col + i : junk + lane) = nv;
+      }
+    }
+    __syncthreads();
+  }
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) Sg[(int64_t)i * P + j] = S[ram_col(j, P) + i - j];
+}
+
+template <typename T, class TINY>
+static int launch_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a,
+                      double g, uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                      uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
+  const size_t bytes = ey_generic_ram_lds(pl);
+  int rc;
+  if ((rc = prep(k_ram<T, TINY>, bytes))) return rc;
+  hipLaunchKernelGGL((k_ram<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target, (T*)chol,
+                     (const T*)z, (const T*)u, a, g, n, (const T*)temp, seed, iter, chain_offset,
+                     (unsigned char*)accepted, (T*)log_rate, run ? *run : one, C);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+
+size_t ey_generic_ram_lds(const ey_plan* pl) {
+  const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
+  return lds_bytes(pl->m, 2, esz) + ram_extra_bytes(pl->m.P, esz);
+}
+
+int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                   uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                   void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  if (pl->m.P > RAM_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "RAM: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
+                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
+  if (ey_generic_ram_lds(pl) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "RAM: the factor and the model's evaluation image (" +
+                                    std::to_string(ey_generic_ram_lds(pl)) + " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_TINY_DISPATCH(launch_ram, pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted,
+                          log_rate, s, run);
+}

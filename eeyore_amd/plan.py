@@ -321,6 +321,44 @@ class Plan:
         self._stepped()
         return out
 
+    def _chol(self, chol, C):
+        if (chol.device != self.device or chol.dtype != self.dtype or not chol.is_contiguous()
+                or tuple(chol.shape) != (C, self.P, self.P)):
+            raise ValueError(f"chol must be a contiguous [{C}, {self.P}, {self.P}] tensor of the plan's dtype on its device")
+
+    def ram_step(self, theta, target, chol, n, a=0.234, g=0.7, z=None, u=None, temp=None, seed=0, it=0, chain_offset=0,
+                 flags=0, out=None):
+        """One RAM.draw (eeyore/samplers/ram.py:38-70) of every chain (ey_ram_step): theta [C,P], target [C] and the
+        lower-triangular factor chol [C,P,P] are updated in place; ``n`` is the adaptation index counter.idx + 1 - offset."""
+        C = self._theta(theta)
+        self._chol(chol, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
+        temp, u = self._opt(temp, C), self._opt(u, C)
+        L.check(L.lib().ey_ram_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(chol), L.ptr(z), L.ptr(u), float(a),
+                                    float(g), int(n), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
+                                    L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)), "ey_ram_step")
+        self._stepped()
+        return out
+
+    def ram_run(self, theta, target, chol, n, n_iters, a=0.234, g=0.7, temp=None, seed=0, it=0, chain_offset=0, flags=0,
+                samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
+        """``n_iters`` RAM iterations of every chain in one launch (ey_ram_run), adaptation indices n, n + 1, ...;
+        records as in ``hmc_run``."""
+        C = self._theta(theta)
+        self._chol(chol, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8))
+        temp = self._opt(temp, C)
+        n_iters = int(n_iters)
+        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
+        L.check(L.lib().ey_ram_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(chol), float(a), float(g), int(n),
+                                   L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
+                                   L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
+                                   L.ptr(out["accepted"]), _stream(self.device)), "ey_ram_run")
+        self._stepped(n_iters)
+        return out
+
     def pt_swap_decide(self, ell_i, ell_j, t_i, t_j, u, dlogq=None):
         return pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=dlogq)
 

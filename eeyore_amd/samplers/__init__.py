@@ -3,3 +3,4 @@ from .hmc import HMC
 from .mala import MALA
 from .metropolis_hastings import MetropolisHastings
 from .power_posterior_sampler import PowerPosteriorSampler
+from .ram import RAM

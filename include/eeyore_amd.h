@@ -175,6 +175,22 @@ int ey_mh_run(ey_plan* plan, void* theta, void* target, const void* scale, const
               uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets,
               void* accepted_rec, void* accept_count, void* accepted, void* stream);
 
+/* One RAM.draw (eeyore/samplers/ram.py:38-70) for C chains. chol [C,P,P] lower-triangular, in/out; z [C,P], u [C]
+ * replace the random draws (NULL => Philox, as ey_mh_step); n = counter.idx + 1 - offset (>= 1); 0 < a < 1.
+ * Robust adaptive Metropolis (Vihola 2012): propose theta + chol z, accept iff log(u) < log_rate, then always adapt
+ * chol <- chol(chol (I + h (alpha - a) z z^T / |z|^2) chol^T), h = min(1, P n^-g), alpha = min(1, exp(log_rate)) with a
+ * NaN log_rate counting as 1.  Only the lower triangle of chol is read or written.  Served by one kernel for every model
+ * (whatever ey_plan_kernel reports) with P <= 128 whose factor fits beside its evaluation image in LDS;
+ * EY_ERR_UNSUPPORTED otherwise, before any launch.  log_rate [C] output may be NULL. */
+int ey_ram_step(ey_plan* plan, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                uint32_t flags, void* accepted, void* log_rate, void* stream);
+/* n_iters iterations in one launch (adaptation index n, n+1, ...), records as ey_mh_run; bit-identical to n_iters
+ * calls of ey_ram_step with z = u = NULL. */
+int ey_ram_run(ey_plan* plan, void* theta, void* target, void* chol, double a, double g, uint64_t n, const void* temp,
+               int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
+               void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream);
+
 /* PowerPosteriorSampler.between_chain_move (eeyore/samplers/power_posterior_sampler.py:135-163) decision for C
  * chain pairs: log_rate = dlogq + (t_i - t_j) * (ell_j - ell_i) with ell the UNTEMPERED log-target; swap iff
  * log(u) < log_rate (:160).  All arrays [C] of `dtype`; dlogq may be NULL (symmetric partner choice). */
