@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 EY_F32, EY_F64 = 0, 1
 EY_ACT_NONE, EY_ACT_SIGMOID, EY_ACT_TANH, EY_ACT_RELU = 0, 1, 2, 3
 EY_LIK_BCE_SUM, EY_LIK_CE_SUM = 0, 1
-EY_RECOMPUTE_INITIAL_GRAD, EY_FORCE_GENERIC = 1, 2
+EY_RECOMPUTE_INITIAL_GRAD, EY_FORCE_GENERIC, EY_GIBBS_CARRY = 1, 2, 4
 
 # every symbol include/eeyore_amd.h declares: (name, restype, argtypes)
 _vp, _i, _i64, _u64, _u32, _d = ct.c_void_p, ct.c_int, ct.c_int64, ct.c_uint64, ct.c_uint32, ct.c_double
@@ -52,6 +52,11 @@ SYMBOLS = {
     "ey_ram_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
     "ey_ram_run": (_i, [_vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
                         _vp]),
+    "ey_gibbs_table_create": (_i, [ct.POINTER(_vp), _i64, _i, _vp, _vp, _vp, _i, _i]),
+    "ey_gibbs_table_destroy": (_i, [_vp]),
+    "ey_gibbs_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
+    "ey_gibbs_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_philox_uniform_blocks": (_i, [_vp, _i64, _i64, _u64, _u64, _u64, _i, _vp]),
     "ey_inse_univariate": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "ey_plan_attach_da": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _i]),
     "ey_inse_multivariate": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -19,7 +19,7 @@ class _Offload:
 
 class ChainBuffer(Chain):
     """Chain storage for C chains advanced together: device buffers ``sample [iters, C, P]``,
-    ``target_val [iters, C]``, ``accepted [iters, C]`` grown geometrically, written by one ``copy_`` per saved
+    ``target_val [iters, C]``, ``accepted [iters, C]`` (``[iters, C, S]`` for Gibbs' S sub-steps) grown geometrically, written by one ``copy_`` per saved
     iteration (no host sync).  ``get_chain(c)`` / ``to_chainlists()`` give the reference's per-chain views
     (eeyore/chains/chain_list.py, chain_lists.py)."""
 
@@ -115,7 +115,8 @@ class ChainBuffer(Chain):
         return batched.mc_se(self.get_samples())
 
     def acceptance_rate(self):
-        """Per-chain acceptance [C] = sum(accepted) / num_samples (chain_list.py:94-96)."""
+        """Per-chain acceptance [C] = sum(accepted) / num_samples (chain_list.py:94-96); [C, S], per sub-step, when the
+        sampler stores S flags per draw (Gibbs)."""
         return self.get_accepted().to(torch.float64).mean(0)
 
     # ---- off the device without stalling the sampler (SURVEY.md 8f row 2)
@@ -152,6 +153,11 @@ class ChainBuffer(Chain):
         """``runNN``-style directories of the reference's CSV files, one per chain (eeyore/chains/chain_file.py:21-45):
         the whole buffer goes to the host in one asynchronous copy, the files are written from there."""
         from pathlib import Path
+        if 'accepted' in self.bufs and self.bufs['accepted'].dim() > 2:
+            raise NotImplementedError(
+                "ChainBuffer.to_chainfiles: 'accepted' holds one flag per sub-step (Gibbs, [iters, C, S]) and the "
+                "reference's accepted.csv holds one integer per row; write get_accepted() yourself or store the chain "
+                "without the 'accepted' key")
         host = self.offload_async().wait()
         cs = range(self.num_chains()) if chains is None else chains
         width = len(str(self.num_chains()))
@@ -167,9 +173,9 @@ class ChainBuffer(Chain):
         vals = {}
         for k in self.keys:
             col = self.bufs[k][:self.n, c]
-            if k == 'accepted':
+            if k == 'accepted' and col.dim() == 1:
                 vals[k] = [int(a) for a in col.cpu().tolist()]
-            else:
+            else:  # vectors, and Gibbs' flag per sub-step [S] (a tensor per draw, as the reference stores it)
                 vals[k] = list(col.unbind(0))
         return ChainList(keys=self.keys, vals=vals)
 

@@ -679,6 +679,112 @@ int ey_ram_run(ey_plan* pl, void* theta, void* target, void* chol, double a, dou
                   nullptr, stream, &run, "ey_ram_run");
 }
 
+// ---- Gibbs: blockwise random-walk Metropolis on k_gibbs (ey_generic.hip) for every model, whatever plan.kernel says
+int ey_gibbs_table_create(ey_gibbs_table** out, int64_t P, int S, const int32_t* blk_off, const int32_t* blk_idx,
+                          const double* blk_scale, int dtype, int device_id) {
+  const char* who = "ey_gibbs_table_create";
+  if (!out) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  *out = nullptr;
+  if (!blk_off || !blk_idx || !blk_scale) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": bad dtype");
+  if (P < 1 || P > 0x7fffffffLL) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": P out of range");
+  if (S < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a table needs at least one block (S >= 1)");
+  if (blk_off[0] != 0) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": blk_off[0] must be 0");
+  std::vector<char> seen((size_t)P, 0);
+  for (int s = 0; s < S; ++s) {
+    if (blk_off[s + 1] <= blk_off[s])
+      EY_FAIL(EY_ERR_INVALID, std::string(who) + ": block " + std::to_string(s) + " is empty (blk_off must increase)");
+    if ((int64_t)blk_off[s + 1] > P)  // disjoint blocks of [0, P) hold at most P indices: nothing beyond is read
+      EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the blocks hold more than P indices, so they overlap");
+    if (!(blk_scale[s] > 0.0) || !std::isfinite(blk_scale[s]))
+      EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the scale of block " + std::to_string(s) +
+                                  " must be a positive finite number");
+    for (int j = blk_off[s]; j < blk_off[s + 1]; ++j) {
+      const int i = blk_idx[j];
+      if (i < 0 || i >= P)
+        EY_FAIL(EY_ERR_INVALID, std::string(who) + ": index " + std::to_string(i) + " of block " + std::to_string(s) +
+                                    " is outside [0, " + std::to_string(P) + ")");
+      if (seen[i])
+        EY_FAIL(EY_ERR_INVALID, std::string(who) + ": parameter " + std::to_string(i) + " is in two blocks (block " +
+                                    std::to_string(s) + " is the second)");
+      seen[i] = 1;
+    }
+  }
+  EY_HIP(hipSetDevice(device_id));
+  ey_gibbs_table* tb = new ey_gibbs_table();
+  tb->P = P; tb->S = S; tb->n_idx = blk_off[S]; tb->dtype = dtype; tb->device = device_id;
+  tb->d_off = tb->d_idx = nullptr; tb->d_scale = nullptr;
+  const size_t esz = dtype == EY_F32 ? 4 : 8;
+  std::vector<float> sf(blk_scale, blk_scale + S);
+  hipError_t e = hipMalloc((void**)&tb->d_off, sizeof(int) * (S + 1));
+  if (e == hipSuccess) e = hipMalloc((void**)&tb->d_idx, sizeof(int) * tb->n_idx);
+  if (e == hipSuccess) e = hipMalloc(&tb->d_scale, esz * S);
+  if (e == hipSuccess) e = hipMemcpy(tb->d_off, blk_off, sizeof(int) * (S + 1), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(tb->d_idx, blk_idx, sizeof(int) * tb->n_idx, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(tb->d_scale, dtype == EY_F32 ? (const void*)sf.data() : (const void*)blk_scale, esz * S,
+                  hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    ey_gibbs_table_destroy(tb);
+    EY_FAIL(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  *out = tb;
+  return EY_OK;
+}
+
+int ey_gibbs_table_destroy(ey_gibbs_table* tb) {
+  if (!tb) return EY_OK;
+  if (tb->d_off) (void)hipFree(tb->d_off);
+  if (tb->d_idx) (void)hipFree(tb->d_idx);
+  if (tb->d_scale) (void)hipFree(tb->d_scale);
+  delete tb;
+  return EY_OK;
+}
+
+static int gibbs_impl(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
+                      const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                      void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
+  int rc = check_ready(pl, C, who);
+  if (rc < 0) return rc;
+  if (!tb) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null block table");
+  if (tb->P != pl->m.P || tb->dtype != pl->dtype || tb->device != pl->device)
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the block table was built for another model size, dtype or device");
+  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
+  if (ey_generic_gibbs_lds(pl, tb) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": the model's evaluation image and the block table do not fit the "
+                                                   "160 KiB LDS of a CU");
+  if (rc) return EY_OK;  // C == 0
+  EyVariantScope vs(pl);
+  if (!theta || !target || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if ((rc = moments_check(pl, C, who))) return rc;
+  if (pl->mom_s1 && run && run->n_iters > 1 && !run->samples)
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": attached moments with n_iters > 1 need the samples record");
+  EY_HIP(hipSetDevice(pl->device));
+  rc = ey_generic_gibbs(pl, tb, theta, target, z, u, (flags & EY_GIBBS_CARRY) != 0, temp, C, seed, iter, chain_offset,
+                        accepted, log_rate, pl->mom_s1 ? pl->mom_acc : nullptr, (hipStream_t)stream, run);
+  if (rc || !pl->mom_s1) return rc;
+  // s1, s2 from the state(s) the draws left; the kernel has added the accepted fractions to acc
+  if (!run || run->n_iters == 1)
+    return ey_stats_update(theta, nullptr, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr, stream);
+  return ey_stats_update_run(run->samples, nullptr, run->n_iters, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr,
+                             stream);
+}
+
+int ey_gibbs_step(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
+                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                  void* accepted, void* log_rate, void* stream) {
+  return gibbs_impl(pl, tb, theta, target, z, u, temp, C, seed, iter, chain_offset, flags, accepted, log_rate, stream,
+                    nullptr, "ey_gibbs_step");
+}
+
+int ey_gibbs_run(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* temp, int64_t C,
+                 uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                 void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  return gibbs_impl(pl, tb, theta, target, nullptr, nullptr, temp, C, seed, iter, chain_offset, flags, accepted, nullptr,
+                    stream, &run, "ey_gibbs_run");
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------- small kernels
@@ -718,7 +824,34 @@ __global__ void k_philox_uniform(T* out, int64_t C, uint64_t seed, uint64_t iter
   out[c] = ey_rng_uniform<T>(r);
 }
 
+template <typename T>
+__global__ void k_philox_uniform_blocks(T* out, int64_t C, int64_t S, uint64_t seed, uint64_t iter, uint64_t chain_offset) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < C * S; k += stride) {
+    const int64_t c = k / S, s = k - c * S;
+    const EyRng r = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    out[k] = ey_rng_uniform_at<T>(r, (uint32_t)s);
+  }
+}
+
 extern "C" {
+
+int ey_philox_uniform_blocks(void* out, int64_t C, int64_t S, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                             int dtype, void* stream) {
+  if (!out) EY_FAIL(EY_ERR_INVALID, "ey_philox_uniform_blocks: null argument");
+  if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, "ey_philox_uniform_blocks: bad dtype");
+  if (C <= 0 || S <= 0) return EY_OK;
+  const int64_t nblk = (C * S + 255) / 256;
+  const dim3 grid((unsigned)(nblk < 65536 ? nblk : 65536));
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == EY_F32)
+    hipLaunchKernelGGL(k_philox_uniform_blocks<float>, grid, dim3(256), 0, s, (float*)out, C, S, seed, iter, chain_offset);
+  else
+    hipLaunchKernelGGL(k_philox_uniform_blocks<double>, grid, dim3(256), 0, s, (double*)out, C, S, seed, iter,
+                       chain_offset);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
 
 int ey_pt_swap_decide(const void* ell_i, const void* ell_j, const void* t_i, const void* t_j, const void* dlogq,
                       const void* u, int64_t C, int dtype, void* swap, void* log_rate, void* stream) {

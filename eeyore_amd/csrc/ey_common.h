@@ -184,6 +184,20 @@ int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const voi
                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                    void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
+// node-blocked Metropolis-within-Gibbs (k_gibbs): blockwise random-walk Metropolis over a table of disjoint index sets
+struct ey_gibbs_table {
+  int64_t P;       // parameters of the model the table was built for
+  int S, n_idx;    // sub-steps per draw, indices in all of them together
+  int dtype, device;
+  int* d_off;      // [S + 1] device: sub-step s owns d_idx[d_off[s] .. d_off[s + 1])
+  int* d_idx;      // [n_idx] device
+  void* d_scale;   // [S] device, of dtype
+};
+size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb);  // dynamic LDS of one chain's workgroup
+int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
+                     bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                     void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run = nullptr);
+
 // layerwise batched-GEMM kernels for large models, f32 (ey_large.hip)
 bool ey_large_needed(const ey_plan* pl, int nvec = 3);  // true when the generic kernels cannot hold the model in LDS
 int ey_large_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
@@ -336,5 +350,23 @@ template <>
 __device__ inline double ey_rng_uniform<double>(const EyRng& r) {
   uint32_t o[4];
   ey_philox4x32_10(0u, r.c1, r.c2, r.c3, r.k0, r.k1, o);
+  return (double)(((uint64_t)o[0] << 21) | (o[1] >> 11)) * 1.1102230246251565e-16;
+}
+
+// The accept stream at block word `block`: Gibbs draws one accept variate per sub-step s of a (chain, iteration) with
+// block = s, so sub-step 0 draws ey_rng_uniform's variate (the same arithmetic on the words of Philox block `block`).
+template <typename T>
+__device__ inline T ey_rng_uniform_at(const EyRng& r, uint32_t block);
+
+template <>
+__device__ inline float ey_rng_uniform_at<float>(const EyRng& r, uint32_t block) {
+  uint32_t o[4];
+  ey_philox4x32_10(block, r.c1, r.c2, r.c3, r.k0, r.k1, o);
+  return (float)(o[0] >> 8) * 5.9604644775390625e-08f;
+}
+template <>
+__device__ inline double ey_rng_uniform_at<double>(const EyRng& r, uint32_t block) {
+  uint32_t o[4];
+  ey_philox4x32_10(block, r.c1, r.c2, r.c3, r.k0, r.k1, o);
   return (double)(((uint64_t)o[0] << 21) | (o[1] >> 11)) * 1.1102230246251565e-16;
 }

@@ -1258,3 +1258,136 @@ int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const voi
   return EY_TINY_DISPATCH(launch_ram, pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted,
                           log_rate, s, run);
 }
+
+// ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
+// Gibbs.draw (eeyore/samplers/gibbs.py:67-102): per draw, S accept/reject sub-steps, each a Normal random-walk proposal
+// for one block of parameters and one evaluation of the whole log-target.  The kernel knows nothing of nodes: it walks a
+// table of disjoint index sets (ey_gibbs_table), so that parameter i consumes normal i of the iteration's stream whichever
+// block holds it.  One wave per chain, no row-wave form.  LDS: the proposal vector in l.th, the CURRENT state in l.gr
+// (eval_target<GRAD = false> never touches it), the iteration's normals in l.a, then the table.  Global theta is read once
+// per launch and written once per iteration.  carry = false: a rejected block of the proposal vector is restored from the
+// state (a valid Metropolis-within-Gibbs); carry = true: it stays for the rest of the draw, as the reference leaves it
+// (DESIGN.md 4.11, 8), and the proposal vector restarts from the state at the next draw (`proposed = current.clone()`).
+static size_t gibbs_table_bytes(int S, int n_idx, size_t esz) {
+  return (((size_t)4 * (S + 1 + n_idx) + 7) & ~(size_t)7) + esz * (size_t)S;
+}
+
+template <typename T, class TINY>
+__global__ void __launch_bounds__(WAVE) k_gibbs(EyModel m, T* theta, T* target, const T* z_in, const T* u_in,
+                                                const int* blk_off, const int* blk_idx, const T* blk_scale, int S,
+                                                int n_idx, int carry, const T* temp, uint64_t seed, uint64_t iter0,
+                                                uint64_t chain_offset, unsigned char* accepted, T* log_rate_o,
+                                                double* mom_acc, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, 3);
+  const int P = m.P;
+  T* cur = l.gr;
+  T* zs = l.a;
+  unsigned char* tb = smem + lds_bytes(m, 3, sizeof(T));
+  int* off = reinterpret_cast<int*>(tb);
+  int* idx = off + S + 1;
+  T* scl = reinterpret_cast<T*>(tb + (((size_t)4 * (S + 1 + n_idx) + 7) & ~(size_t)7));
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  for (int s = lane; s <= S; s += WAVE) off[s] = blk_off[s];
+  for (int j = lane; j < n_idx; j += WAVE) idx[j] = blk_idx[j];
+  for (int s = lane; s < S; s += WAVE) scl[s] = blk_scale[s];
+  for (int i = lane; i < P; i += WAVE) {
+    const T v = theta[c * P + i];
+    cur[i] = v;
+    l.th[i] = v;
+  }
+  T t_state = target[c];
+  __syncthreads();
+  for (int it = 0; it < run.n_iters; ++it) {
+    const uint64_t iter = iter0 + (uint64_t)it;
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    if (!z_in) fill_normals<T>(zs, rn, P);
+    else {
+      for (int i = lane; i < P; i += WAVE) zs[i] = z_in[c * P + i];
+      __syncthreads();
+    }
+    int n_acc = 0;
+    for (int s = 0; s < S; ++s) {
+      const int o0 = off[s], o1 = off[s + 1];
+      const T sc = scl[s];
+      for (int j = o0 + lane; j < o1; j += WAVE) {
+        const int i = idx[j];
+        l.th[i] = l.th[i] + sc * zs[i];  // NormalKernel(proposed[idx], scale).sample() (gibbs.py:84-86)
+      }
+      __syncthreads();
+      const T tv = eval_target<T, false, TINY>(m, l, l.th, cur, ht, tc, nullptr, nullptr);
+      const T log_rate = tv - t_state;  // :89
+      const T u = u_in ? u_in[c * S + s] : ey_rng_uniform_at<T>(ru, (uint32_t)s);
+      const bool acc = Num<T>::log(u) < log_rate;  // :90; a NaN log-rate rejects
+      if (acc) {
+        t_state = tv;
+        for (int j = o0 + lane; j < o1; j += WAVE) {
+          const int i = idx[j];
+          cur[i] = l.th[i];
+        }
+      } else if (!carry) {
+        for (int j = o0 + lane; j < o1; j += WAVE) {
+          const int i = idx[j];
+          l.th[i] = cur[i];
+        }
+      }
+      n_acc += acc ? 1 : 0;
+      if (lane == 0) {
+        accepted[c * S + s] = acc ? 1 : 0;
+        if (log_rate_o) log_rate_o[c * S + s] = log_rate;
+        if (run.accepted) static_cast<unsigned char*>(run.accepted)[((int64_t)it * C + c) * S + s] = acc ? 1 : 0;
+        if (run.accept_count && acc) run.accept_count[c * S + s] += 1;
+      }
+      __syncthreads();
+    }
+    T* so = run.samples ? static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P : nullptr;
+    for (int i = lane; i < P; i += WAVE) {
+      const T v = cur[i];
+      theta[c * P + i] = v;
+      if (so) so[i] = v;
+      if (carry) l.th[i] = v;  // the next draw's proposal vector starts from the state (:78)
+    }
+    if (lane == 0) {
+      target[c] = t_state;
+      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+      if (mom_acc) mom_acc[c] += (double)n_acc / (double)S;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, class TINY>
+static int launch_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
+                        bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                        void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run) {
+  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
+  const size_t bytes = ey_generic_gibbs_lds(pl, tb);
+  int rc;
+  if ((rc = prep(k_gibbs<T, TINY>, bytes))) return rc;
+  hipLaunchKernelGGL((k_gibbs<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
+                     (const T*)z, (const T*)u, (const int*)tb->d_off, (const int*)tb->d_idx, (const T*)tb->d_scale, tb->S,
+                     tb->n_idx, carry ? 1 : 0, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted,
+                     (T*)log_rate, mom_acc, run ? *run : one, C);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+
+size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb) {
+  const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
+  return lds_bytes(pl->m, 3, esz) + gibbs_table_bytes(tb->S, tb->n_idx, esz);
+}
+
+int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
+                     bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                     void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run) {
+  if (ey_generic_gibbs_lds(pl, tb) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the model's evaluation image and the block table (" +
+                                    std::to_string(ey_generic_gibbs_lds(pl, tb)) +
+                                    " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_TINY_DISPATCH(launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter, chain_offset, accepted,
+                          log_rate, mom_acc, s, run);
+}

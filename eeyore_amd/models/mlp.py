@@ -84,6 +84,47 @@ class MLP(BayesianModel):
     def num_hidden_layers(self):
         return len(self.hp.dims) - 2
 
+    # -- parameter blocks for Gibbs: one block per non-input node, holding the node's incoming weights and its bias
+    #    (eeyore/models/mlp.py:56-103).  Blocks are numbered layer by layer, node by node.
+    def _layer_width(self, l):
+        """Parameters of layer l: dims[l+1] rows of dims[l] weights, then dims[l+1] biases when the layer has them."""
+        return (self.hp.dims[l] + (1 if self.hp.bias[l] else 0)) * self.hp.dims[l + 1]
+
+    def num_par_blocks(self):
+        return sum(self.hp.dims[1:])
+
+    def layer_and_node_from_par_block(self, b):
+        """(layer, node within the layer) of block b.  The node is b minus the nodes of all earlier layers; the reference
+        takes b modulo that count, which is the same number only while no layer is wider than all layers before it
+        together."""
+        if not 0 <= b < self.num_par_blocks():
+            raise IndexError(f"parameter block {b} out of range [0, {self.num_par_blocks()})")
+        first = 0
+        for l, width in enumerate(self.hp.dims[1:]):
+            if b < first + width:
+                return l, b - first
+            first += width
+
+    def starting_par_block_idx(self, l):
+        """Index of the first parameter of layer l."""
+        return sum(self._layer_width(k) for k in range(l))
+
+    def starting_par_block_indices(self):
+        """First parameter index of the input-side layers 0 .. num_hidden_layers() (the output layer's start is not listed,
+        as in the reference)."""
+        return [self.starting_par_block_idx(l) for l in range(self.num_hidden_layers() + 1)]
+
+    def annotated_par_block_indices(self, b):
+        l, n = self.layer_and_node_from_par_block(b)
+        start, fan_in = self.starting_par_block_idx(l), self.hp.dims[l]
+        indices = [start + n * fan_in + i for i in range(fan_in)]
+        if self.hp.bias[l]:
+            indices.append(start + fan_in * self.hp.dims[l + 1] + n)
+        return indices, l, n
+
+    def par_block_indices(self, b):
+        return self.annotated_par_block_indices(b)[0]
+
     def _plan(self, x, y):
         """This model's C-ABI plan with the current prior and, when given, the (x, y) batch attached."""
         plan = self._hip_plan

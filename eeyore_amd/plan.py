@@ -16,6 +16,44 @@ def _stream(device):
     return ct.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+GIBBS_MODES = {'intended': 0, 'reference': L.EY_GIBBS_CARRY}
+
+
+def gibbs_table_arrays(blocks, scales):
+    """(blk_off [S+1] int32, blk_idx int32, blk_scale [S] double) as ctypes arrays from a list of index lists and one
+    scale per list -- the host form ey_gibbs_table_create validates."""
+    blocks = [[int(i) for i in b] for b in blocks]
+    scales = [float(v) for v in scales]
+    if len(scales) != len(blocks):
+        raise ValueError(f"a Gibbs table needs one scale per block: {len(blocks)} blocks, {len(scales)} scales")
+    off = [0]
+    for b in blocks:
+        off.append(off[-1] + len(b))
+    flat = [i for b in blocks for i in b]
+    return ((ct.c_int32 * len(off))(*off), (ct.c_int32 * max(len(flat), 1))(*flat),
+            (ct.c_double * max(len(scales), 1))(*scales))
+
+
+class GibbsTable:
+    """Device copy of a Gibbs block table (ey_gibbs_table): built once per sampler, freed with the object."""
+
+    def __init__(self, plan, blocks, scales):
+        off, idx, scl = gibbs_table_arrays(blocks, scales)
+        self.S = len(off) - 1
+        self.blocks = [list(b) for b in blocks]
+        self.handle = ct.c_void_p()
+        L.check(L.lib().ey_gibbs_table_create(ct.byref(self.handle), plan.P, self.S, off, idx, scl, _DT[plan.dtype],
+                                              plan.device.index), "ey_gibbs_table_create")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and self.handle.value:
+                L.lib().ey_gibbs_table_destroy(self.handle)
+                self.handle = ct.c_void_p()
+        except Exception:
+            pass
+
+
 class Plan:
     def __init__(self, dims, bias, acts, likelihood, dtype, device):
         self.device = torch.device(device)
@@ -359,6 +397,62 @@ class Plan:
         self._stepped(n_iters)
         return out
 
+    def gibbs_table(self, blocks, scales):
+        """The device block table of a Gibbs sampler on this plan (ey_gibbs_table_create): ``blocks`` is a list of S
+        disjoint index lists in visiting order, ``scales`` one positive proposal scale per block."""
+        return GibbsTable(self, blocks, scales)
+
+    def _gibbs_args(self, table, C, mode):
+        if not isinstance(table, GibbsTable):
+            raise ValueError("table must be a GibbsTable (Plan.gibbs_table)")
+        if mode not in GIBBS_MODES:
+            raise ValueError("mode must be 'intended' (a rejected block is restored) or 'reference' (it is carried)")
+        return table.S, GIBBS_MODES[mode]
+
+    def gibbs_step(self, theta, target, table, z=None, u=None, mode='intended', temp=None, seed=0, it=0, chain_offset=0,
+                   flags=0, out=None):
+        """One Gibbs.draw (eeyore/samplers/gibbs.py:67-102) of every chain (ey_gibbs_step): the table's S Metropolis
+        sub-steps; theta [C,P] and target [C] are updated in place.  z [C,P] and u [C,S] replace the random draws.
+        Returns accepted [C,S] uint8 and log_rate [C,S]."""
+        C = self._theta(theta)
+        S, carry = self._gibbs_args(table, C, mode)
+        if out is None:
+            out = dict(accepted=self.empty(C, S, dtype=torch.uint8), log_rate=self.empty(C, S))
+        for name, t, shape in (("z", z, (C, self.P)), ("u", u, (C, S))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != self.dtype or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous {shape} tensor of the plan's dtype on its device")
+        temp = self._opt(temp, C)
+        L.check(L.lib().ey_gibbs_step(self.handle, table.handle, L.ptr(theta), L.ptr(target), L.ptr(z), L.ptr(u),
+                                      L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags) | carry,
+                                      L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)),
+                "ey_gibbs_step")
+        self._stepped()
+        return out
+
+    def gibbs_run(self, theta, target, table, n_iters, mode='intended', temp=None, seed=0, it=0, chain_offset=0, flags=0,
+                  samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
+        """``n_iters`` Gibbs draws of every chain in one launch (ey_gibbs_run); records as in ``hmc_run`` except that
+        ``accepted_rec`` is [n_iters, C, S] and ``accept_count`` [C, S]."""
+        C = self._theta(theta)
+        S, carry = self._gibbs_args(table, C, mode)
+        if out is None:
+            out = dict(accepted=self.empty(C, S, dtype=torch.uint8))
+        temp = self._opt(temp, C)
+        n_iters = int(n_iters)
+        self._records(n_iters, C, samples, targets, None, None)
+        for name, t, shape, dt in (("accepted_rec", accepted_rec, (n_iters, C, S), torch.uint8),
+                                   ("accept_count", accept_count, (C, S), torch.int32)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the plan's device")
+        L.check(L.lib().ey_gibbs_run(self.handle, table.handle, L.ptr(theta), L.ptr(target), L.ptr(temp), C, int(seed),
+                                     int(it), int(chain_offset), int(flags) | carry, n_iters, L.ptr(samples),
+                                     L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
+                                     _stream(self.device)), "ey_gibbs_run")
+        self._stepped(n_iters)
+        return out
+
     def pt_swap_decide(self, ell_i, ell_j, t_i, t_j, u, dlogq=None):
         return pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=dlogq)
 
@@ -373,6 +467,14 @@ class Plan:
         L.check(L.lib().ey_philox_uniform(L.ptr(out), C, int(seed), int(it), int(chain_offset), _DT[self.dtype],
                                           _stream(self.device)), "ey_philox_uniform")
         return out
+
+    def philox_uniform_blocks(self, C, S, seed, it, chain_offset=0):
+        """u [C, S]: the accept variates of the S sub-steps of a Gibbs draw (ey_philox_uniform_blocks)."""
+        out = self.empty(C, S)
+        L.check(L.lib().ey_philox_uniform_blocks(L.ptr(out), C, int(S), int(seed), int(it), int(chain_offset),
+                                                 _DT[self.dtype], _stream(self.device)), "ey_philox_uniform_blocks")
+        return out
+
 
 
 def pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=None):

@@ -4,3 +4,4 @@ from .mala import MALA
 from .metropolis_hastings import MetropolisHastings
 from .power_posterior_sampler import PowerPosteriorSampler
 from .ram import RAM
+from .gibbs import Gibbs

@@ -172,7 +172,7 @@ class SingleChainSerialSampler(SerialSampler):
         rec = {}
         if savestate:
             views = self.chain.block(k, dict(sample=self._theta, target_val=self._target,
-                                             accepted=torch.empty(self.num_chains, dtype=torch.uint8,
+                                             accepted=torch.empty(self._accepted_shape(), dtype=torch.uint8,
                                                                   device=self._theta.device)))
             rec = dict(samples=views.get('sample'), targets=views.get('target_val'),
                        accepted_rec=views.get('accepted'))
@@ -192,6 +192,10 @@ class SingleChainSerialSampler(SerialSampler):
 
     def _run_block(self, plan, k, rec):
         raise NotImplementedError
+
+    def _accepted_shape(self):
+        """Shape of one draw's accept flags for all chains: one flag per chain (Gibbs stores one per sub-step)."""
+        return (self.num_chains,)
 
     def _configure(self, model, dataloader, theta0, chain, rng, seed, chain_offset, temperature):
         self.model = model

@@ -27,6 +27,7 @@ extern "C" {
 #endif
 
 typedef struct ey_plan ey_plan;
+typedef struct ey_gibbs_table ey_gibbs_table;
 
 enum ey_status {
   EY_OK = 0,
@@ -77,7 +78,9 @@ enum ey_row_waves { EY_ROW_WAVES_OFF = 0, EY_ROW_WAVES_ON = 1, EY_ROW_WAVES_AUTO
 enum ey_flags {
   EY_RECOMPUTE_INITIAL_GRAD = 1, /* HMC: re-evaluate the gradient at the start of the trajectory exactly as
                                     hmc.py:104 does (L+1 evaluations) instead of using the cached `grad` (L) */
-  EY_FORCE_GENERIC = 2           /* route to the generic VALU kernels even when an MFMA kernel covers the plan */
+  EY_FORCE_GENERIC = 2,          /* route to the generic VALU kernels even when an MFMA kernel covers the plan */
+  EY_GIBBS_CARRY = 4             /* ey_gibbs_*: a rejected sub-step's proposal stays in the proposal vector for the rest
+                                    of the draw, as eeyore/samplers/gibbs.py:67-102 leaves it (mode 'reference') */
 };
 
 int ey_version(void);
@@ -191,6 +194,37 @@ int ey_ram_run(ey_plan* plan, void* theta, void* target, void* chol, double a, d
                int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
                void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream);
 
+/* The block table of a Gibbs sampler: S sub-steps in visiting order, sub-step s proposing for the parameters
+ * blk_idx[blk_off[s] .. blk_off[s+1]) with the Normal scale blk_scale[s].  The table is model-agnostic (blockwise
+ * random-walk Metropolis over any list of DISJOINT index sets of [0, P)); the node numbering of an MLP lives with the
+ * caller.  blk_off [S+1] and blk_idx [blk_off[S]] int32, blk_scale [S] double: HOST arrays owned by the caller, read
+ * during this call only.  The call validates them (EY_ERR_INVALID: S < 1, blk_off[0] != 0, an empty block, an index out of
+ * [0, P), an index in two blocks, a scale that is not a positive finite number) and uploads a device copy, converted to
+ * `dtype`, which the table object owns until ey_gibbs_table_destroy (call it once no launch that uses it is in flight). */
+int ey_gibbs_table_create(ey_gibbs_table** out, int64_t P, int S, const int32_t* blk_off, const int32_t* blk_idx,
+                          const double* blk_scale, int dtype, int device_id);
+int ey_gibbs_table_destroy(ey_gibbs_table* table);
+
+/* One Gibbs.draw (eeyore/samplers/gibbs.py:67-102) for C chains: S Metropolis sub-steps in the table's order.  Sub-step s
+ * adds blk_scale[s] * z[c, i] to the proposal vector for the i of its block, evaluates the log-target of the whole
+ * proposal vector, and accepts iff log(u[c, s]) < log_target - target[c] (a NaN rejects).  On accept the block enters the
+ * state and target[c] takes the value; on reject the block of the proposal vector is restored from the state, or, with
+ * EY_GIBBS_CARRY in flags, left as proposed for the rest of the draw as the reference leaves it.  z [C,P], u [C,S] replace
+ * the random draws; NULL => Philox: parameter i uses normal i of the iteration (ey_philox_normal), sub-step s the accept
+ * stream at block word s (ey_philox_uniform_blocks; sub-step 0 draws ey_philox_uniform's variate).  accepted [C,S] uint8;
+ * log_rate [C,S] may be NULL.  Attached moments: s1, s2 take the state after the draw, acc the accepted fraction of its S
+ * sub-steps.  Served by one kernel for every model that fits in LDS with the table beside it (whatever ey_plan_kernel
+ * reports), EY_ERR_UNSUPPORTED otherwise; a table built for another P, dtype or device is EY_ERR_INVALID; both before
+ * any launch. */
+int ey_gibbs_step(ey_plan* plan, const ey_gibbs_table* table, void* theta, void* target, const void* z, const void* u,
+                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                  void* accepted, void* log_rate, void* stream);
+/* n_iters draws in one launch; records samples [n,C,P], targets [n,C], accepted_rec [n,C,S] uint8, accept_count [C,S]
+ * int32 (+=), each may be NULL; bit-identical to n_iters calls of ey_gibbs_step with z = u = NULL. */
+int ey_gibbs_run(ey_plan* plan, const ey_gibbs_table* table, void* theta, void* target, const void* temp, int64_t C,
+                 uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                 void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream);
+
 /* PowerPosteriorSampler.between_chain_move (eeyore/samplers/power_posterior_sampler.py:135-163) decision for C
  * chain pairs: log_rate = dlogq + (t_i - t_j) * (ell_j - ell_i) with ell the UNTEMPERED log-target; swap iff
  * log(u) < log_rate (:160).  All arrays [C] of `dtype`; dlogq may be NULL (symmetric partner choice). */
@@ -204,10 +238,14 @@ int ey_philox_normal(void* out, int64_t C, int64_t P, uint64_t seed, uint64_t it
                      void* stream);
 int ey_philox_uniform(void* out, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, int dtype,
                       void* stream);
+/* out[c, s] = U[0,1) accept variate of sub-step s of that chain and iteration (what ey_gibbs_step's u = NULL uses): the
+ * accept stream with Philox block word s, so out[:, 0] is ey_philox_uniform's variate. */
+int ey_philox_uniform_blocks(void* out, int64_t C, int64_t S, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                             int dtype, void* stream);
 /* One Philox4x32-10 block on the HOST (no device needed): out[4] = philox(counter[4], key[2]), the function the device
  * streams above are built on (Salmon et al. 2011; checked against Random123's known-answer vectors in the tests).
  * counter = (block, chain_lo, iter_lo, iter_hi << 8 | stream | chain_hi << 20), key = (seed_lo, seed_hi), stream 0 =
- * normals, 1 = accept uniform. */
+ * normals, 1 = accept uniform (block 0; block s for sub-step s of a Gibbs draw). */
 int ey_philox_block(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 
 /* Running per-chain moments for ChainLists.mean / R-hat style summaries (eeyore/chains/chain_lists.py:65-66,
