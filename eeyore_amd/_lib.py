@@ -52,6 +52,10 @@ SYMBOLS = {
     "ey_ram_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
     "ey_ram_run": (_i, [_vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
                         _vp]),
+    "ey_am_step": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32,
+                        _vp, _vp, _vp, _vp, _vp]),
+    "ey_am_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,
+                       _vp, _vp, _vp, _vp, _vp]),
     "ey_gibbs_table_create": (_i, [ct.POINTER(_vp), _i64, _i, _vp, _vp, _vp, _i, _i]),
     "ey_gibbs_table_destroy": (_i, [_vp]),
     "ey_gibbs_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),

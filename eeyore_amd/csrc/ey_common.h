@@ -184,6 +184,25 @@ int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const voi
                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                    void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
+// adaptive Metropolis (k_am): the state and the settings of AM.draw beside theta and target, whatever plan.kernel says
+struct EyAm {
+  void* mean;           // [C, P] running_mean, in/out
+  void* cov_sum;        // [C, P, P] sum of theta theta^T, in/out (j <= i only)
+  void* cov;            // [C, P, P] the proposal covariance, in/out (j <= i only)
+  int* num_accepted;    // [C] int32, in/out
+  const void* cov0;     // [P, P] or [C, P, P]: the transformed initial covariance
+  int cov0_per_chain;
+  double l, b, c, eps;
+  int64_t t0, idx, offset;
+  const void *z, *u_mix, *u;  // recorded draws [C, P], [C], [C], or null
+  unsigned char* branch;      // [C] 0 isotropic, 1 factor, 2 breakdown; or null
+  int* breakdowns;            // [C] int32 (+=)
+};
+size_t ey_generic_am_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
+int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
+                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
+                  const EyRun* run = nullptr);
+
 // node-blocked Metropolis-within-Gibbs (k_gibbs): blockwise random-walk Metropolis over a table of disjoint index sets
 struct ey_gibbs_table {
   int64_t P;       // parameters of the model the table was built for

@@ -1391,3 +1391,261 @@ int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* t
   return EY_TINY_DISPATCH(launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter, chain_offset, accepted,
                           log_rate, mom_acc, s, run);
 }
+
+// ----------------------------------------------------------------------------------------------- adaptive Metropolis
+// AM.draw (eeyore/samplers/am.py:61-107; Haario et al. 2001) with the transform cov -> cov + eps I fused.
+// n = idx + 1 - offset.  Proposal: theta + c z while n <= t0; afterwards one more uniform u_mix picks theta + c z
+// (u_mix < l) or theta + (b L) z with L = chol(cov).  Accept as MH does; num_accepted counts accepts of idx > 0.  Then,
+// accepted or not:  mean <- ((n - 1) mean + theta) / n,  cov_sum <- cov_sum + theta theta^T,  and from n >= t0 on
+// cov <- cov0' while num_accepted == 0, else (cov_sum - n mean mean^T) / (n - 1) + eps I -- the reference's order of
+// operations in the working dtype.
+// One wave per chain, lane <-> row (rows lane and lane + 64: P <= 128), as k_ram.  LDS after the MH image: two packed
+// lower triangles in ram_col order -- cov_sum, and a work triangle that holds cov and is factorised IN PLACE only in a draw
+// that takes the L z branch (such a draw has n > t0, so its adaptation rebuilds the triangle: between draws it is
+// always cov) -- then running_mean, z and a slot per lane for the stores of rows above a column.  l.gr keeps the current
+// state (eval_target<GRAD = false> never touches it).  cov_sum, running_mean and cov are read once per launch from dense
+// row-major global state and written back once at its end; only j <= i is touched.
+// Factorisation: left-looking column Cholesky.  For column j lane i >= j forms A[i,j] - sum_{k<j} L[i,k] L[j,k] (L[j,k]
+// one address for the wave, L[i,k] consecutive along a column), the pivot is broadcast from its lane, tested, and the
+// column scaled by the reciprocal of its root.  A pivot that is not > 0 (NaN included) is a breakdown: the draw proposes
+// theta + c z, the chain's breakdown counter grows by one, and the adaptation repairs the triangle.
+__host__ __device__ static size_t am_extra_bytes(int P, size_t esz) {
+  const size_t packed = ((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3, Ppad = (P + 3) & ~3;
+  return esz * (2 * packed + 2 * Ppad + WAVE);
+}
+
+template <typename T, class TINY>
+__global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyAm am, const T* temp, uint64_t seed,
+                                             uint64_t iter0, uint64_t chain_offset, unsigned char* accepted,
+                                             T* log_rate_o, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, 2);
+  const int P = m.P;
+  const size_t packed = ((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3;
+  const int Ppad = (P + 3) & ~3;
+  T* CS = reinterpret_cast<T*>(smem + lds_bytes(m, 2, sizeof(T)));
+  T* W = CS + packed;
+  T* mean = W + packed;
+  T* zs = mean + Ppad;
+  T* junk = zs + Ppad;
+  T* cur = l.gr;
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int R = P > WAVE ? 2 : 1;  // rows per lane
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  T* CSg = static_cast<T*>(am.cov_sum) + c * (int64_t)P * P;
+  T* Wg = static_cast<T*>(am.cov) + c * (int64_t)P * P;
+  T* mg = static_cast<T*>(am.mean) + c * (int64_t)P;
+  const T* c0g = static_cast<const T*>(am.cov0) + (am.cov0_per_chain ? c * (int64_t)P * P : 0);
+  const T* z_in = static_cast<const T*>(am.z);
+  const T* umix_in = static_cast<const T*>(am.u_mix);
+  const T* u_in = static_cast<const T*>(am.u);
+  const T lT = (T)am.l, bT = (T)am.b, cT = (T)am.c, epsT = (T)am.eps;
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) {
+      CS[ram_col(j, P) + i - j] = CSg[(int64_t)i * P + j];
+      W[ram_col(j, P) + i - j] = Wg[(int64_t)i * P + j];
+    }
+  for (int i = lane; i < P; i += WAVE) {
+    mean[i] = mg[i];
+    cur[i] = theta[c * P + i];
+  }
+  T t_state = target[c];
+  int nacc = am.num_accepted[c];
+  int nbreak = am.breakdowns[c];
+  int branch = 0;
+  __syncthreads();
+  for (int it = 0; it < run.n_iters; ++it) {
+    const uint64_t iter = iter0 + (uint64_t)it;
+    const int64_t idx = am.idx + it;
+    const int64_t n = idx + 1 - am.offset;
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    if (!z_in) fill_normals<T>(zs, rn, P);  // am.py:67
+    else {
+      for (int i = lane; i < P; i += WAVE) zs[i] = z_in[c * P + i];
+      __syncthreads();
+    }
+    branch = 0;
+    if (n > am.t0) {  // :68-73: the mixture uniform is drawn only here
+      const T um = umix_in ? umix_in[c] : ey_rng_uniform_at<T>(ru, 1u);
+      branch = um < lT ? 0 : 1;
+    }
+    if (branch == 1) {
+      // ---- W <- chol(W), column by column; every quantity that steers the loop is wave-uniform
+      const T* ck0 = W;
+      bool ok = true;
+      for (int j = 0; j < P; ++j) {
+        T* colj = W + ram_col(j, P) - j;
+        T sum[2] = {T(0), T(0)};
+        const T* colk = ck0;
+        for (int k = 0; k < j; ++k) {
+          const T ljk = colk[j];
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+            const int i = lane + r * WAVE;
+            const bool on = i >= j && i < P;
+            const T lik = colk[on ? i : j];
+            sum[r] += lik * ljk;
+          }
+          colk += P - k - 1;
+        }
+        T s[2] = {T(0), T(0)};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+          const int i = lane + r * WAVE;
+          const bool on = i >= j && i < P;
+          s[r] = colj[on ? i : j] - sum[r];
+        }
+        const T d = __shfl(j >= WAVE ? s[1] : s[0], j & (WAVE - 1), WAVE);
+        if (!(d > T(0))) {
+          ok = false;
+          break;
+        }
+        const T piv = Num<T>::sqrt(d);
+        const T rp = T(1) / piv;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+          const int i = lane + r * WAVE;
+          const bool on = i >= j && i < P;
+          const T v = i == j ? piv : s[r] * rp;
+          *(on ? colj + i : junk + lane) = v;
+        }
+        __syncthreads();
+      }
+      if (!ok) {
+        branch = 2;
+        nbreak += 1;
+      }
+    }
+    if (branch == 1) {  // theta + (b L) z (:73): a column sweep, one running sum per row
+      T acc[2] = {T(0), T(0)};
+      for (int j = 0; j < P; ++j) {
+        const T zj = zs[j];
+        const T* col = W + ram_col(j, P) - j;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+          const int i = lane + r * WAVE;
+          const bool on = i >= j && i < P;
+          const T s = col[on ? i : j];
+          acc[r] += (bT * (on ? s : T(0))) * zj;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+        const int i = lane + r * WAVE;
+        if (i < P) l.th[i] = cur[i] + acc[r];
+      }
+    } else {
+      for (int i = lane; i < P; i += WAVE) l.th[i] = cur[i] + cT * zs[i];  // :70, :75 -- k_mh's proposal with scale c
+    }
+    __syncthreads();
+    const T tv = eval_target<T, false, TINY>(m, l, l.th, cur, ht, tc, nullptr, nullptr);
+    const T log_rate = tv - t_state;  // :78
+    const T u = u_in ? u_in[c] : ey_rng_uniform<T>(ru);
+    const bool acc_ = Num<T>::log(u) < log_rate;  // :80; a NaN log-rate rejects
+    if (acc_) {
+      t_state = tv;
+      if (idx > 0) nacc += 1;  // :85 looks at the absolute index
+      for (int i = lane; i < P; i += WAVE) {
+        const T v = l.th[i];
+        cur[i] = v;
+        theta[c * P + i] = v;
+      }
+    }
+    // ---- adaptation (:91-101), accepted or not
+    const T nT = (T)n, n1T = (T)(n - 1);
+    for (int i = lane; i < P; i += WAVE) mean[i] = (n1T * mean[i] + cur[i]) / nT;
+    __syncthreads();  // the state and the mean of every row are visible
+    if (run.samples) {
+      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
+      for (int i = lane; i < P; i += WAVE) so[i] = cur[i];
+    }
+    if (lane == 0) {
+      if (acc_) target[c] = tv;
+      accepted[c] = acc_ ? 1 : 0;
+      if (log_rate_o) log_rate_o[c] = log_rate;
+      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
+      if (run.accept_count && acc_) run.accept_count[c] += 1;
+    }
+    const int rebuild = n >= am.t0 ? (nacc == 0 ? 1 : 2) : 0;
+    T ti[2], mi[2];
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      ti[r] = cur[i < P ? i : 0];
+      mi[r] = mean[i < P ? i : 0];
+    }
+    for (int j = 0; j < P; ++j) {
+      const T tj = cur[j], mj = mean[j];
+      T* cs = CS + ram_col(j, P) - j;
+      T* w = W + ram_col(j, P) - j;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        if (r >= R) break;  // wave-uniform: P <= 64 has no second row
+        const int i = lane + r * WAVE;
+        const bool on = i >= j && i < P;
+        const int ii = on ? i : j;
+        const T sv = cs[ii] + ti[r] * tj;  // :94
+        T* dst = on ? cs + i : junk + lane;
+        *dst = sv;
+        if (rebuild) {
+          T wv;
+          if (rebuild == 1) wv = c0g[(int64_t)ii * P + j];                         // :97
+          else wv = (sv - nT * (mi[r] * mj)) / n1T + (ii == j ? epsT : T(0));  // :59, then the ridge
+          T* dw = on ? w + i : junk + lane;
+          *dw = wv;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) {
+      CSg[(int64_t)i * P + j] = CS[ram_col(j, P) + i - j];
+      Wg[(int64_t)i * P + j] = W[ram_col(j, P) + i - j];
+    }
+  for (int i = lane; i < P; i += WAVE) mg[i] = mean[i];
+  if (lane == 0) {
+    am.num_accepted[c] = nacc;
+    am.breakdowns[c] = nbreak;
+    if (am.branch) am.branch[c] = (unsigned char)branch;
+  }
+}
+
+template <typename T, class TINY>
+static int launch_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
+                     uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
+                     const EyRun* run) {
+  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
+  const size_t bytes = ey_generic_am_lds(pl);
+  int rc;
+  if ((rc = prep(k_am<T, TINY>, bytes))) return rc;
+  hipLaunchKernelGGL((k_am<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target, am,
+                     (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : one,
+                     C);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+
+size_t ey_generic_am_lds(const ey_plan* pl) {
+  const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
+  return lds_bytes(pl->m, 2, esz) + am_extra_bytes(pl->m.P, esz);
+}
+
+int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
+                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  if (pl->m.P > RAM_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "AM: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
+                                    std::to_string(RAM_MAX_P) + " parameters (the covariance lives in LDS)");
+  if (ey_generic_am_lds(pl) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "AM: the two covariance triangles and the model's evaluation image (" +
+                                    std::to_string(ey_generic_am_lds(pl)) + " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_TINY_DISPATCH(launch_am, pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
+}

@@ -453,6 +453,69 @@ class Plan:
         self._stepped(n_iters)
         return out
 
+    def _am_state(self, C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns):
+        P = self.P
+        for name, t, shape, dt in (("running_mean", running_mean, (C, P), self.dtype),
+                                   ("cov_sum", cov_sum, (C, P, P), self.dtype), ("cov", cov, (C, P, P), self.dtype),
+                                   ("num_accepted", num_accepted, (C,), torch.int32),
+                                   ("breakdowns", breakdowns, (C,), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the plan's device")
+        if (cov0.dtype != self.dtype or not cov0.is_contiguous() or cov0.device != self.device
+                or tuple(cov0.shape) not in ((P, P), (C, P, P))):
+            raise ValueError(f"cov0 must be a contiguous [{P}, {P}] or [{C}, {P}, {P}] tensor of the plan's dtype on its "
+                             "device")
+        return int(cov0.dim() == 3)
+
+    def am_step(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, l=0.05, b=1., c=1., eps=0.,
+                t0=2, offset=0, z=None, u_mix=None, u=None, temp=None, seed=0, it=0, chain_offset=0, flags=0,
+                breakdowns=None, out=None):
+        """One AM.draw (eeyore/samplers/am.py:61-107) of every chain (ey_am_step) with the ridge cov + eps I fused:
+        theta [C,P], target [C], running_mean [C,P], cov_sum and cov [C,P,P] (lower triangles) and num_accepted [C] int32
+        are updated in place; ``cov0`` is the transformed initial covariance, ``idx`` the counter index of the draw.
+        ``breakdowns`` [C] int32 is incremented for a chain whose covariance could not be factorised."""
+        C = self._theta(theta)
+        if breakdowns is None:
+            breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
+        per_chain = self._am_state(C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C),
+                       branch=self.empty(C, dtype=torch.uint8))
+        out["breakdowns"] = breakdowns
+        temp, u, u_mix = self._opt(temp, C), self._opt(u, C), self._opt(u_mix, C)
+        L.check(L.lib().ey_am_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum),
+                                   L.ptr(cov), L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c),
+                                   float(eps), int(t0), int(idx), int(offset), L.ptr(z), L.ptr(u_mix), L.ptr(u),
+                                   L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
+                                   L.ptr(out["accepted"]), L.ptr(out.get("log_rate")), L.ptr(out.get("branch")),
+                                   L.ptr(breakdowns), _stream(self.device)), "ey_am_step")
+        self._stepped()
+        return out
+
+    def am_run(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, n_iters, l=0.05, b=1., c=1.,
+               eps=0., t0=2, offset=0, temp=None, seed=0, it=0, chain_offset=0, flags=0, breakdowns=None, samples=None,
+               targets=None, accepted_rec=None, accept_count=None, out=None):
+        """``n_iters`` AM iterations of every chain in one launch (ey_am_run), counter indices idx, idx + 1, ...; records
+        as in ``hmc_run``."""
+        C = self._theta(theta)
+        if breakdowns is None:
+            breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
+        per_chain = self._am_state(C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8))
+        out["breakdowns"] = breakdowns
+        temp = self._opt(temp, C)
+        n_iters = int(n_iters)
+        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
+        L.check(L.lib().ey_am_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum),
+                                  L.ptr(cov), L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c),
+                                  float(eps), int(t0), int(idx), int(offset), L.ptr(temp), C, int(seed), int(it),
+                                  int(chain_offset), int(flags), n_iters, L.ptr(samples), L.ptr(targets),
+                                  L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]), L.ptr(breakdowns),
+                                  _stream(self.device)), "ey_am_run")
+        self._stepped(n_iters)
+        return out
+
     def pt_swap_decide(self, ell_i, ell_j, t_i, t_j, u, dlogq=None):
         return pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=dlogq)
 

@@ -225,6 +225,32 @@ int ey_gibbs_run(ey_plan* plan, const ey_gibbs_table* table, void* theta, void* 
                  uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
                  void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream);
 
+/* One AM.draw (eeyore/samplers/am.py:61-107, Haario et al.'s adaptive Metropolis) for C chains, with the transform
+ * cov -> cov + eps I fused.  State, all in/out: running_mean [C,P], cov_sum [C,P,P], cov [C,P,P] (only j <= i of the two
+ * matrices is read or written), num_accepted [C] int32.  cov0 is the TRANSFORMED initial covariance, [P,P] or, with
+ * cov0_per_chain != 0, [C,P,P].  With n = idx + 1 - offset (>= 1, idx >= 0): the proposal is theta + c z while n <= t0;
+ * afterwards u_mix < l proposes theta + c z and anything else theta + (b chol(cov)) z.  Accept iff log(u) < log_rate;
+ * num_accepted counts accepts of idx > 0.  Then running_mean <- ((n-1) running_mean + theta) / n, cov_sum += theta theta^T
+ * and, from n >= t0 on, cov <- cov0 while num_accepted == 0, else (cov_sum - n mean mean^T) / (n-1) + eps I.
+ * A pivot of the factorisation that is not > 0 (NaN included) makes the draw propose theta + c z and adds one to
+ * breakdowns [C] int32.  z [C,P], u_mix [C], u [C] replace the random draws (NULL => Philox: u_mix is word block 1 of
+ * the accept stream).  Outputs: accepted [C] uint8; log_rate [C] and branch [C] uint8 (0 isotropic, 1 factor,
+ * 2 breakdown) may be NULL.  t0 >= 2, 0 <= l <= 1, b and c finite, eps finite and >= 0: EY_ERR_INVALID otherwise.
+ * Served by one kernel for every model (whatever ey_plan_kernel reports) with P <= 128 whose two covariance triangles fit
+ * beside its evaluation image in LDS; EY_ERR_UNSUPPORTED otherwise, before any launch. */
+int ey_am_step(ey_plan* plan, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,
+               const void* cov0, int cov0_per_chain, double l, double b, double c, double eps, int64_t t0, int64_t idx,
+               int64_t offset, const void* z, const void* u_mix, const void* u, const void* temp, int64_t C,
+               uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate,
+               void* branch, void* breakdowns, void* stream);
+/* n_iters iterations in one launch (idx, idx+1, ...), records as ey_mh_run; bit-identical to n_iters calls of
+ * ey_am_step with z = u_mix = u = NULL. */
+int ey_am_run(ey_plan* plan, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,
+              const void* cov0, int cov0_per_chain, double l, double b, double c, double eps, int64_t t0, int64_t idx,
+              int64_t offset, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+              uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count,
+              void* accepted, void* breakdowns, void* stream);
+
 /* PowerPosteriorSampler.between_chain_move (eeyore/samplers/power_posterior_sampler.py:135-163) decision for C
  * chain pairs: log_rate = dlogq + (t_i - t_j) * (ell_j - ell_i) with ell the UNTEMPERED log-target; swap iff
  * log(u) < log_rate (:160).  All arrays [C] of `dtype`; dlogq may be NULL (symmetric partner choice). */
