@@ -1,6 +1,8 @@
 """The fused 16x16x4 matrix-core kernels (ey_fused16.hip: d0-H-H-dK, H in {16, 32, 64}, f32 and f64, CE or BCE, sigmoid /
 tanh / relu) through the C ABI against the C oracle, and against the generic kernels on the same inputs.
-f64 within 1e-10 relative (the reference's default dtype, eeyore/models/model.py:7), f32 within the stated 2e-4."""
+f64 within 1e-10 relative (the reference's default dtype, eeyore/models/model.py:7), f32 within the stated 2e-4.
+C = 11 (and 9) here gives grid = 11: only wave 0 of each workgroup has a chain and no wave takes a second one, so these
+tests exercise wave 0 / round 0 only; tests/test_persistent_slots.py covers the other wave slots and chain rounds."""
 import os
 
 import numpy as np

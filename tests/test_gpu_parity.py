@@ -911,8 +911,15 @@ def test_mfma32_more_chains_than_resident_waves():
     C = 4500
     th = 0.2 * pl.philox_normal(C, seed=21, it=0)
     t, g = pl.log_target_grad(th)
-    tg, gg = pl.log_target_grad(th[:64].clone())
-    assert torch.equal(t[:64], tg) and torch.equal(g[:64], gg)  # a chain's result does not depend on its slot
+    # a chain's result does not depend on its slot: 64 chains from every round of the launch, run alone
+    from tests.test_persistent_slots import slot
+    grid = min(C, torch.cuda.get_device_properties(0).multi_processor_count)
+    stride = 8 * grid
+    offsets = [0] + [min(r * stride + 3 * grid + grid // 2, C - 64) for r in range(1, (C - 1) // stride + 1)]
+    assert {slot(c0, grid, 8)[2] for c0 in offsets} == set(range((C - 1) // stride + 1)) and len(offsets) >= 2
+    for c0 in offsets:
+        tg, gg = pl.log_target_grad(th[c0:c0 + 64].clone())
+        assert torch.equal(t[c0:c0 + 64], tg) and torch.equal(g[c0:c0 + 64], gg), (c0, slot(c0, grid, 8))
     a = [th.clone(), t.clone(), g.clone()]
     b = [th.clone(), t.clone(), g.clone()]
     oa = pl.hmc_step(*a, 0.03, 4, seed=5, it=1)
