@@ -38,6 +38,9 @@ SYMBOLS = {
     "ey_mala_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
     "ey_mh_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
     "ey_pt_swap_decide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "ey_pt_ladder_create": (_i, [_vp, _vp, _i, _i, ct.POINTER(_vp)]),
+    "ey_pt_ladder_destroy": (_i, [_vp]),
+    "ey_pt_between": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ey_philox_normal": (_i, [_vp, _i64, _i64, _u64, _u64, _u64, _i, _vp]),
     "ey_philox_uniform": (_i, [_vp, _i64, _u64, _u64, _u64, _i, _vp]),
     "ey_philox_block": (_i, [ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_uint32)]),

@@ -1,2 +1,2 @@
 from .storage import Chain, ChainFile, ChainList, ChainLists
-from .chain_buffer import ChainBuffer
+from .chain_buffer import ChainBuffer, ChainBufferView

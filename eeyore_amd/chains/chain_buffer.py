@@ -181,3 +181,27 @@ class ChainBuffer(Chain):
 
     def to_chainlists(self):
         return ChainLists.from_chain_list([self.get_chain(c) for c in range(self.num_chains())], keys=self.keys)
+
+
+class ChainBufferView(ChainBuffer):
+    """Chains [lo, hi) of another ChainBuffer as a ChainBuffer of their own: the per-temperature chains of a
+    PowerPosteriorSampler whose K x R chains record into ONE buffer [iters, K * R, ...].  It shares the backing buffer's
+    memory and length, so it is always as long as what the backing buffer has recorded, and every accessor of ChainBuffer
+    works on it (the device statistics copy their strided input into contiguous memory themselves).  It records nothing:
+    writing goes through the backing buffer."""
+
+    def __init__(self, base, lo, hi):
+        self.base, self.lo, self.hi = base, lo, hi
+
+    keys = property(lambda self: self.base.keys)
+    capacity = property(lambda self: self.base.capacity)
+    n = property(lambda self: self.base.n)
+
+    @property
+    def bufs(self):
+        return {k: v[:, self.lo:self.hi] for k, v in self.base.bufs.items()}
+
+    def _read_only(self, *args, **kwargs):
+        raise RuntimeError("a ChainBufferView records nothing: reset, reserve or update the ChainBuffer it is a view of")
+
+    reset = rewind = reserve = update = block = commit = detach_and_update = drop_front = _read_only

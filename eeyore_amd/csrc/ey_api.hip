@@ -842,11 +842,8 @@ __global__ void k_pt_swap(const T* ell_i, const T* ell_j, const T* t_i, const T*
                           int64_t C, unsigned char* swap, T* log_rate) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  // power_posterior_sampler.py:135-141 with T_k = t_k * ell:  dlogq + (t_i - t_j) * (ell_j - ell_i)
-  T lr = (t_i[c] - t_j[c]) * (ell_j[c] - ell_i[c]);
-  if (dlogq) lr += dlogq[c];
-  const T lu = sizeof(T) == 4 ? (T)logf((float)u[c]) : (T)log((double)u[c]);
-  swap[c] = lu < lr ? 1 : 0;  // :160
+  T lr;
+  swap[c] = ey_pt_decide<T>(ell_i[c], ell_j[c], t_i[c], t_j[c], dlogq ? dlogq + c : nullptr, u[c], &lr) ? 1 : 0;
   if (log_rate) log_rate[c] = lr;
 }
 

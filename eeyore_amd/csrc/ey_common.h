@@ -275,6 +275,7 @@ int ey_fused16_leapfrog(ey_plan* pl, void* theta, void* p, double step, const vo
 // lane needs never depends on which lane asks, so every kernel layout reproduces the same stream.
 #define EY_STREAM_NORMAL 0u
 #define EY_STREAM_UNIFORM 1u
+#define EY_STREAM_PT 2u  // the between-chain move of a tempering ladder (k_pt_between): Philox block i = step i of the move
 
 struct EyRng {
   uint32_t k0, k1;  // key = seed
@@ -388,4 +389,18 @@ __device__ inline double ey_rng_uniform_at<double>(const EyRng& r, uint32_t bloc
   uint32_t o[4];
   ey_philox4x32_10(block, r.c1, r.c2, r.c3, r.k0, r.k1, o);
   return (double)(((uint64_t)o[0] << 21) | (o[1] >> 11)) * 1.1102230246251565e-16;
+}
+
+// The exchange decision of PowerPosteriorSampler.between_chain_move (power_posterior_sampler.py:135-141,160) with
+// T_k = t_k * ell:  log_rate = dlogq + (t_i - t_j) * (ell_j - ell_i), swap iff log(u) < log_rate.  k_pt_swap (ey_api.hip) and
+// k_pt_between (ey_pt.hip) both decide through this function.  Contraction is off: the product is rounded before dlogq
+// is added, as the torch expressions of the host path round it, whichever kernel the function is inlined into.
+template <typename T>
+__device__ inline bool ey_pt_decide(T ell_i, T ell_j, T t_i, T t_j, const T* dlogq, T u, T* log_rate) {
+#pragma clang fp contract(off)
+  T lr = (t_i - t_j) * (ell_j - ell_i);
+  if (dlogq) lr += *dlogq;
+  const T lu = sizeof(T) == 4 ? (T)logf((float)u) : (T)log((double)u);
+  *log_rate = lr;
+  return lu < lr;  // :160
 }

@@ -54,6 +54,36 @@ class GibbsTable:
             pass
 
 
+class PtLadder:
+    """Device copy of a tempering ladder (ey_pt_ladder) for ``pt_between``: temperatures ``t`` [K] and partner weights
+    ``q`` [K, K] (row i: the weights with which chain i proposes its partner, diagonal ignored), validated by the library
+    on the host.  Built once per sampler, freed with the object."""
+
+    def __init__(self, t, q, dtype, device):
+        if dtype not in _DT:
+            raise ValueError(f"unsupported dtype {dtype}")
+        self.dtype, self.device = dtype, torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        t = [float(v) for v in t]
+        self.K = K = len(t)
+        q = [[float(v) for v in row] for row in q]
+        if len(q) != K or any(len(row) != K for row in q):
+            raise ValueError(f"q must be [{K}, {K}], one row of partner weights per temperature")
+        self.handle = ct.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ey_pt_ladder_create((ct.c_double * K)(*t), (ct.c_double * (K * K))(*[v for row in q for v in row]),
+                                                K, _DT[dtype], ct.byref(self.handle)), "ey_pt_ladder_create")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and self.handle.value:
+                L.lib().ey_pt_ladder_destroy(self.handle)
+                self.handle = ct.c_void_p()
+        except Exception:
+            pass
+
+
 class Plan:
     def __init__(self, dims, bias, acts, likelihood, dtype, device):
         self.device = torch.device(device)
@@ -519,6 +549,13 @@ class Plan:
     def pt_swap_decide(self, ell_i, ell_j, t_i, t_j, u, dlogq=None):
         return pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=dlogq)
 
+    def pt_ladder(self, t, q):
+        """The device ladder of a power-posterior sampler on this plan's dtype and device (ey_pt_ladder_create)."""
+        return PtLadder(t, q, self.dtype, self.device)
+
+    def pt_between(self, ladder, theta, target, grad=None, **kw):
+        return pt_between(ladder, theta, target, grad, **kw)
+
     def philox_normal(self, C, seed, it, chain_offset=0):
         out = self.empty(C, self.P)
         L.check(L.lib().ey_philox_normal(L.ptr(out), C, self.P, int(seed), int(it), int(chain_offset), _DT[self.dtype],
@@ -539,7 +576,6 @@ class Plan:
         return out
 
 
-
 def pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=None):
     """PowerPosteriorSampler.between_chain_move decision (power_posterior_sampler.py:135-163) for C pairs."""
     C = ell_i.shape[0]
@@ -551,3 +587,38 @@ def pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=None):
     L.check(L.lib().ey_pt_swap_decide(*[L.ptr(a) for a in args], C, _DT[dt], L.ptr(swap), L.ptr(log_rate), _stream(dev)),
             "ey_pt_swap_decide")
     return swap, log_rate
+
+
+def pt_between(ladder, theta, target, grad=None, partners=None, u=None, seed=0, it=0, replica_offset=0, rec_theta=None,
+               rec_target=None, outputs=True):
+    """PowerPosteriorSampler.between_chain_moves for every replica of the ladder in ONE launch (ey_pt_between): theta
+    [K*R, P], target [K*R] and grad [K*R, P] (or None) are updated in place, row k * R + r being temperature k of replica r.
+    ``partners`` [K, R] int32 and ``u`` [K, R] replace the Philox draws keyed (seed, replica_offset + r, it); ``rec_theta``
+    [K*R, P] / ``rec_target`` [K*R] are the record of the draw the move belongs to and take the exchanged rows too.
+    Returns dict(partners, u, swap, log_rate), each [K, R] (an empty dict with ``outputs=False``).  Nothing here
+    synchronises with the device."""
+    if not isinstance(ladder, PtLadder):
+        raise ValueError("ladder must be a PtLadder (Plan.pt_ladder)")
+    K, dt, dev = ladder.K, ladder.dtype, ladder.device
+    if theta.dim() != 2 or theta.shape[0] % K:
+        raise ValueError(f"theta must be [K * R, P] with K = {K}")
+    C, P = theta.shape
+    R = C // K
+
+    def want(name, t, shape, dtype=dt):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on the ladder's device")
+
+    for name, t, shape in (("theta", theta, (C, P)), ("target", target, (C,)), ("grad", grad, (C, P)), ("u", u, (K, R)),
+                           ("rec_theta", rec_theta, (C, P)), ("rec_target", rec_target, (C,))):
+        want(name, t, shape)
+    want("partners", partners, (K, R), torch.int32)
+    out = {}
+    if outputs:
+        out = dict(partners=torch.empty(K, R, dtype=torch.int32, device=dev), u=torch.empty(K, R, dtype=dt, device=dev),
+                   swap=torch.empty(K, R, dtype=torch.uint8, device=dev), log_rate=torch.empty(K, R, dtype=dt, device=dev))
+    L.check(L.lib().ey_pt_between(ladder.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), R, P, L.ptr(partners), L.ptr(u),
+                                  int(seed), int(it), int(replica_offset), L.ptr(rec_theta), L.ptr(rec_target),
+                                  L.ptr(out.get("partners")), L.ptr(out.get("u")), L.ptr(out.get("swap")),
+                                  L.ptr(out.get("log_rate")), _stream(dev)), "ey_pt_between")
+    return out

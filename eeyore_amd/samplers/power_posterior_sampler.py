@@ -9,8 +9,25 @@ from .hmc import HMC
 from .mala import MALA
 from .metropolis_hastings import MetropolisHastings
 from .base import SerialSampler
-from eeyore_amd.chains import ChainBuffer, ChainFile
+from eeyore_amd.chains import ChainBuffer, ChainBufferView, ChainFile
 from eeyore_amd.datasets import DataCounter
+
+
+def pt_segments(idx, num_iters, num_burnin_iters, between_step, fused_block):
+    """Cut the draws [idx, num_iters) into the blocks the device run loop issues: ``[(first, count, between)]``.  A block
+    ends with the next draw d that has ``d % between_step == 0`` (its between-chain move follows the block: ``between``),
+    before the burn-in boundary (a block is recorded as a whole or not at all), or after ``fused_block`` draws, whichever
+    comes first."""
+    out = []
+    block = max(1, int(fused_block))
+    while idx < num_iters:
+        to_between = (-idx) % between_step  # draws before the next between-draw
+        end = min(idx + to_between + 1, idx + block, num_iters)
+        if idx < num_burnin_iters:
+            end = min(end, num_burnin_iters)
+        out.append((idx, end - idx, (end - 1) % between_step == 0))
+        idx = end
+    return out
 
 
 class PowerPosteriorSampler(SerialSampler):
@@ -28,11 +45,18 @@ class PowerPosteriorSampler(SerialSampler):
     Categorical(prob ~ exp(-b|i-j|)) (:107-122) and the states of i and j are exchanged iff
     ``log(u) < log q(i|j) - log q(j|i) + (t_i - t_j)(ell(theta_j) - ell(theta_i))`` (:135-141,160; ``ell`` the
     untempered log-target, decided by ``ey_pt_swap_decide``).  An exchange needs no re-evaluation: the tempered
-    target and gradient of a moved state are rescaled by t_new / t_old (the reference re-evaluates, :143-151)."""
+    target and gradient of a moved state are rescaled by t_new / t_old (the reference re-evaluates, :143-151).
+
+    ``between='host'`` (default) makes these moves with a host loop over the temperatures that draws partners and accept
+    variates from torch's global generator.  ``between='device'`` makes the whole move in ONE launch (``ey_pt_between``) that
+    draws them from the Philox stream keyed (seed, replica_offset + r, counter.idx) -- another stream, so other draws, the
+    same algorithm.  In memory (``storage='list'``) the K x R chains then record into one device buffer [iters, K * R, ...]
+    of which ``chains[i]`` are views, and ``run`` issues the within-chain draws between two moves as one launch wherever
+    the within-chain sampler can (its ``fused_block``), with no host synchronisation anywhere in the loop."""
 
     def __init__(self, model, dataloader, samplers, theta0=None, data0=None, counter=None, temperature=None,
                  between_step=10, b=0.5, storage='list', keys=['sample', 'target_val'], path=Path.cwd(), mode='a',
-                 check_input=False, rng=None, seed=0):
+                 check_input=False, rng=None, seed=0, between='host', replica_offset=0):
         super().__init__(counter or DataCounter.from_dataloader(dataloader))
         self.between_step = between_step
         self.b = b
@@ -44,7 +68,10 @@ class PowerPosteriorSampler(SerialSampler):
             raise ValueError("all temperatures must use the same within-chain sampler to be advanced by one fused step")
         if storage not in ('list', 'file'):
             raise ValueError("storage must be 'list' or 'file'")
-        self.storage = storage
+        if between not in ('host', 'device'):
+            raise ValueError("between must be 'host' or 'device'")
+        self.storage, self.between = storage, between
+        self.seed, self.replica_offset = int(seed), int(replica_offset)
         self.keys = list(keys)
         self.dtype, self.device = model.dtype, model.device
         K = self.num_chains
@@ -56,8 +83,11 @@ class PowerPosteriorSampler(SerialSampler):
         theta_all = th.repeat(K, 1).contiguous()  # row k*R + r
         name = self.sampler_names[0]
         kw = [samplers[i][1] for i in range(K)]
+        # between='device' in memory: the within-chain sampler records all K x R chains into one buffer
+        self._backing = ChainBuffer(keys=self.keys) if between == 'device' and storage == 'list' else None
         common = dict(theta0=theta_all, dataloader=dataloader, data0=data0 or next(iter(dataloader)),
-                      counter=self.counter, chain=ChainBuffer(keys=[]), temperature=tvec, rng=rng, seed=seed)
+                      counter=self.counter, chain=self._backing if self._backing is not None else ChainBuffer(keys=[]),
+                      temperature=tvec, rng=rng, seed=seed)
 
         def per_chain(key, default):
             vals = [float(k.get(key, default)) for k in kw]
@@ -82,6 +112,7 @@ class PowerPosteriorSampler(SerialSampler):
         self._tvec = tvec
         self._log_q = torch.tensor(np.log(self._partner_matrix()), dtype=self.dtype, device=self.device)
         self._probs = [torch.tensor(self.eval_categorical_probs(i), dtype=torch.float64) for i in range(K)]
+        self._ladder = None  # between='device': the device ladder, built with the first move (it needs the plan)
 
     def init_chain(self, i, storage, keys, path, mode):
         """The chain of temperature i (power_posterior_sampler.py:57-66): in memory, or appended to
@@ -89,6 +120,9 @@ class PowerPosteriorSampler(SerialSampler):
         replicas of the ladder; on file a single ladder (R = 1) writes the reference's files, R > 1 one directory per
         replica, ``chain<i+1>/replica<r+1>``."""
         if storage == 'list':
+            if self._backing is not None:
+                R = self.num_replicas
+                return ChainBufferView(self._backing, i * R, (i + 1) * R)
             return ChainBuffer(keys=keys)
         folder = path / f"chain{i + 1:0{len(str(self.num_chains))}}"
         if self.num_replicas == 1:
@@ -176,7 +210,21 @@ class PowerPosteriorSampler(SerialSampler):
     def _rand(self, n):
         return torch.rand(n, dtype=self.dtype, device=self.device)
 
+    def _between_on_device(self, x, y, rec_theta=None, rec_target=None):
+        """The whole move as one ``pt_between`` launch on the Philox stream of draw ``counter.idx``."""
+        s = self.sampler
+        plan = self.model._plan(x, y)
+        if self._ladder is None:
+            self._ladder = plan.pt_ladder(self.temperature, self._partner_matrix())
+        out = plan.pt_between(self._ladder, s._theta, s._target, getattr(s, '_grad', None), seed=self.seed,
+                              it=self.counter.idx, replica_offset=self.replica_offset, rec_theta=rec_theta,
+                              rec_target=rec_target)
+        self.last_swaps = [(out['partners'][i], out['swap'][i], out['log_rate'][i]) for i in range(self.num_chains)]
+        self.last_swap_inputs = None  # (the kernel forms its decision inputs step by step; they are not kept)
+
     def between_chain_moves(self, x, y):
+        if self.between == 'device':
+            return self._between_on_device(x, y)
         s = self.sampler
         K, R = self.num_chains, self.num_replicas
         plan = self.model._plan(x, y)
@@ -229,8 +277,47 @@ class PowerPosteriorSampler(SerialSampler):
             self.between_chain_moves(x, y)
 
         if savestate:
-            for i in range(self.num_chains):
-                self.save_state(i)
+            if self._backing is not None:
+                self._save_backing()
+            else:
+                for i in range(self.num_chains):
+                    self.save_state(i)
+
+    def _save_backing(self):
+        s = self.sampler
+        state = {'sample': s._theta, 'target_val': s._target}
+        if 'grad_val' in self.keys:
+            state['grad_val'] = s._grad
+        if 'accepted' in self.keys:
+            state['accepted'] = s.current['accepted']
+        self._backing.update(state)
+
+    def run(self, num_epochs, num_burnin_epochs, verbose=False, verbose_step=100):
+        """As SerialSampler.run.  With ``between='device'`` in memory, where the within-chain sampler can run blocks of
+        draws in one launch, the draws are cut by ``pt_segments``: one launch per block, recorded straight into the backing
+        buffer, and behind a block that ends with a between-draw one ``pt_between`` launch, which also puts the exchanged
+        states into that draw's record (the reference saves a draw's state after its move, :174-182).  The chains are the
+        same, bit for bit, as draw by draw."""
+        s = self.sampler
+        if self._backing is None or not s._can_fuse(verbose):
+            return super().run(num_epochs, num_burnin_epochs, verbose=verbose, verbose_step=verbose_step)
+        counter = self.counter
+        counter.set_epoch_info(num_epochs, num_burnin_epochs)
+        x, y = next(iter(self.dataloader))
+        if not hasattr(self.model._plan(x, y), 'hmc_run'):  # a plan without the block entry points
+            return super().run(num_epochs, num_burnin_epochs, verbose=verbose, verbose_step=verbose_step)
+        for first, count, between in pt_segments(counter.idx, counter.num_iters, counter.num_burnin_iters,
+                                                 self.between_step, s.fused_block):
+            save = first >= counter.num_burnin_iters
+            s._draw_block(x, y, count, savestate=save)
+            for _ in range(count - 1):
+                counter.increment_idx()
+            if between:  # counter.idx is the block's last draw: the move belongs to it
+                rec = self._backing.bufs if save else {}
+                last = self._backing.n - 1
+                self._between_on_device(x, y, rec_theta=rec['sample'][last] if 'sample' in rec else None,
+                                        rec_target=rec['target_val'][last] if 'target_val' in rec else None)
+            counter.increment_idx()
 
     # ---- the multi-chain surface of the reference (eeyore/samplers/multi_chain_serial_sampler.py:10-46); `chain_idx` is
     #      a temperature (default: the last one, the target itself, power_posterior_sampler.py:84-85)
@@ -265,6 +352,8 @@ class PowerPosteriorSampler(SerialSampler):
         self.set_current(theta, data=data)
 
     def reset_chains(self):
+        if self._backing is not None:
+            return self._backing.reset()
         for i, chain in enumerate(self.chains):
             if self.storage == 'list':
                 chain.reset()

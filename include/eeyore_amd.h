@@ -28,6 +28,7 @@ extern "C" {
 
 typedef struct ey_plan ey_plan;
 typedef struct ey_gibbs_table ey_gibbs_table;
+typedef struct ey_pt_ladder ey_pt_ladder;
 
 enum ey_status {
   EY_OK = 0,
@@ -256,6 +257,37 @@ int ey_am_run(ey_plan* plan, void* theta, void* target, void* running_mean, void
  * log(u) < log_rate (:160).  All arrays [C] of `dtype`; dlogq may be NULL (symmetric partner choice). */
 int ey_pt_swap_decide(const void* ell_i, const void* ell_j, const void* t_i, const void* t_j, const void* dlogq,
                       const void* u, int64_t C, int dtype, void* swap /* uint8 [C] */, void* log_rate, void* stream);
+
+/* The ladder of a power-posterior sampler for ey_pt_between: K temperatures t [K] and the partner weights q [K,K], row i
+ * the weights with which chain i proposes its partner (diagonal ignored; a row need not be normalised).  HOST arrays owned
+ * by the caller, read during this call only and validated before anything touches the device (EY_ERR_INVALID: K < 2, a
+ * temperature that is not a positive finite number, a negative or NaN off-diagonal weight, a row whose sum is not positive
+ * and finite; EY_ERR_UNSUPPORTED: K > 1024, the kernel's limit).  The object owns a device copy on the CURRENT device: t and
+ * log(q[i,j] / row sum) rounded to `dtype`, and per row the running sums of q[i,j] / row sum in index order as doubles (the
+ * diagonal adds nothing).  Destroy it once no launch that uses it is in flight. */
+int ey_pt_ladder_create(const double* t, const double* q, int K, int dtype, ey_pt_ladder** out);
+int ey_pt_ladder_destroy(ey_pt_ladder* ladder);
+
+/* PowerPosteriorSampler.between_chain_moves (eeyore/samplers/power_posterior_sampler.py:128-172) for R replicas of the
+ * ladder in one launch.  State row k * R + r is temperature k of replica r: theta [K*R,P], target [K*R] (the TEMPERED
+ * log-targets) and grad [K*R,P] (may be NULL) of the ladder's dtype, updated in place.  For i = 0 .. K-1 in order, step i
+ * sees the exchanges of the steps before it: partner j, ell_i = target_i / t_i, ell_j = target_j / t_j,
+ * log_rate = (log_q[j,i] - log_q[i,j]) + (t_i - t_j) * (ell_j - ell_i) as ey_pt_swap_decide forms it, and iff
+ * log(u) < log_rate the theta rows of i and j trade places, target_i <- target_j * (t_i / t_j),
+ * target_j <- target_i * (t_j / t_i), and the grad rows trade places with the same two factors.
+ * partners [K,R] int32 and u [K,R] of dtype are both given or both NULL (anything else: EY_ERR_INVALID).  A given partner
+ * outside [0, K) or equal to its own i is checked in the kernel and faults nothing: that step exchanges nothing and
+ * reports swap_out = 0 and a NaN log_rate_out.  NULL => Philox keyed (seed, replica_offset + r, iter, stream 2): block
+ * word i gives step i its variates, words 0, 1 a 53-bit double v for the partner (the first index whose running sum
+ * exceeds v; the last index other than i when none does), words 2, 3 the accept variate u as ey_philox_uniform_blocks
+ * converts words 0, 1 -- a replica's bits depend on (seed, replica_offset + r, iter) alone.
+ * rec_theta [K*R,P], rec_target [K*R] (each may be NULL): the record of the draw the move belongs to, which holds the
+ * state from before the move; exchanged rows are written there too and rec_target takes every target.
+ * partners_out [K,R] int32, u_out [K,R], swap_out [K,R] uint8, log_rate_out [K,R]: each may be NULL. */
+int ey_pt_between(const ey_pt_ladder* ladder, void* theta, void* target, void* grad, int64_t R, int64_t P,
+                  const int32_t* partners, const void* u, uint64_t seed, uint64_t iter, uint64_t replica_offset,
+                  void* rec_theta, void* rec_target, int32_t* partners_out, void* u_out, void* swap_out,
+                  void* log_rate_out, void* stream);
 
 /* The in-kernel random streams, exposed so a caller (or a test) can reproduce them:
  *  normal  out[c, i] = N(0,1) for parameter i of chain chain_offset + c at iteration iter (what p0/z = NULL uses)
