@@ -35,6 +35,9 @@ int ey_default_products() {
   return (e && (!strcmp(e, "exact") || !strcmp(e, "1"))) ? EY_PRODUCTS_EXACT : EY_PRODUCTS_BF16X3;
 }
 
+static size_t esize(const ey_plan* pl) { return pl->dtype == EY_F32 ? 4 : 8; }
+static bool is_mix(const ey_plan* pl) { return pl->m.kind == EY_KIND_MIX; }
+
 extern "C" {
 
 int ey_version(void) { return EY_VERSION; }
@@ -79,6 +82,7 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
   m.lik = likelihood;
   m.P = P;
   m.N = 0;
+  m.kind = EY_KIND_MLP;
   m.x = m.y = m.mu = m.inv_var = nullptr;
   m.labels = nullptr;
   m.prior_const = 0.0;
@@ -104,6 +108,109 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
   pl->mfma32_kind = ey_mfma32_kind(pl);
   pl->mfma32_ok = pl->mfma32_kind != 0;
   pl->fused16_ok = ey_fused16_supports(pl);  // also the headline model's second choice (batches beyond mfma32's row limit)
+  *out = pl;
+  return EY_OK;
+}
+
+// A Gaussian-mixture target on theta itself (eeyore/models/distribution_model.py with a closure that is a multivariate
+// normal or a mixture of them).  Everything is validated on the host before the device is touched.
+int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, const double* mean, const double* prec,
+                           int dtype, int device_id) {
+  const char* who = "ey_plan_create_mixture";
+  if (!out) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  *out = nullptr;
+  if (!c || !mean || !prec) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": dtype must be EY_F32 or EY_F64");
+  if (P < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": P must be >= 1");
+  if (M < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": M must be >= 1");
+  if (P > EY_MIX_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": P = " + std::to_string(P) + " exceeds the limit of " +
+                                    std::to_string(EY_MIX_MAX_P) + " parameters");
+  if (M > EY_MIX_MAX_M)
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": M = " + std::to_string(M) + " exceeds the limit of " +
+                                    std::to_string(EY_MIX_MAX_M) + " components");
+  for (int k = 0; k < M; ++k) {
+    if (!std::isfinite(c[k])) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": c[" + std::to_string(k) + "] is not finite");
+    const double* Lk = prec + (size_t)k * P * P;
+    for (int64_t i = 0; i < P; ++i) {
+      if (!std::isfinite(mean[k * P + i]))
+        EY_FAIL(EY_ERR_INVALID, std::string(who) + ": mean of component " + std::to_string(k) + " is not finite");
+      for (int64_t j = 0; j < P; ++j)
+        if (!std::isfinite(Lk[i * P + j]))
+          EY_FAIL(EY_ERR_INVALID, std::string(who) + ": prec of component " + std::to_string(k) + " is not finite");
+    }
+    for (int64_t i = 0; i < P; ++i) {
+      if (!(Lk[i * P + i] > 0.0))
+        EY_FAIL(EY_ERR_INVALID, std::string(who) + ": prec of component " + std::to_string(k) +
+                                    " has a diagonal entry that is not > 0");
+      for (int64_t j = 0; j < i; ++j)
+        if (Lk[i * P + j] != Lk[j * P + i])
+          EY_FAIL(EY_ERR_INVALID, std::string(who) + ": prec of component " + std::to_string(k) +
+                                      " is not exactly symmetric (the kernel reads columns for rows)");
+    }
+  }
+  ey_plan* pl = new ey_plan();
+  EyModel& m = pl->m;
+  memset(&m, 0, sizeof(m));
+  m.kind = EY_KIND_MIX;
+  m.nl = 1;
+  m.dims[0] = m.dims[1] = 1;
+  for (int l = 0; l < EY_MAX_LAYERS; ++l) m.boff[l] = -1;
+  m.P = (int)P;
+  m.N = M;
+  ey_generic_mix_scratch(m);
+  pl->dtype = dtype;
+  pl->device = device_id;
+  pl->has_data = pl->has_prior = true;  // the tables are the data: nothing to attach
+  pl->d_x = pl->d_y = pl->d_mu = pl->d_inv_var = nullptr;
+  pl->d_labels = nullptr;
+  pl->d_xpack = nullptr;
+  pl->cap_N = 0;
+  pl->mfma32_ok = pl->mfma32_data_ok = false;
+  pl->d_work = nullptr;
+  pl->work_bytes = 0;
+  pl->n_cu = 0;
+  // the kernel that needs the most LDS: AM, two packed triangles beside the image
+  if (ey_generic_am_lds(pl) > 160 * 1024 || ey_generic_ram_lds(pl) > 160 * 1024) {
+    const size_t need = std::max(ey_generic_am_lds(pl), ey_generic_ram_lds(pl));
+    delete pl;
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": the evaluation image and AM's covariance triangles (" +
+                                    std::to_string(need) + " bytes) do not fit the 160 KiB LDS of a CU");
+  }
+  // ---- the device from here on
+  auto fail = [&](int code, const std::string& msg) {
+    (void)hipFree(pl->d_x); (void)hipFree(pl->d_y); (void)hipFree(pl->d_mu);
+    delete pl;
+    ey_set_error(msg);
+    return code;
+  };
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess) return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (device_id < 0 || device_id >= ndev) return fail(EY_ERR_INVALID, std::string(who) + ": no such device");
+  hipDeviceProp_t prop;
+  if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess)
+    return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  pl->n_cu = prop.multiProcessorCount;
+  pl->variant = g_ey_default_variant.load() & (32767 & ~1024);
+  pl->products = ey_default_products();
+  pl->row_waves = EY_ROW_WAVES_OFF;
+  // tables of the plan's dtype: computed in double by the caller, rounded once here
+  const size_t es = esize(pl), nm = (size_t)M * P, np = nm * P;
+  std::vector<float> f32;
+  auto upload = [&](void** dst, const double* src, size_t n) -> hipError_t {
+    hipError_t r = hipMalloc(dst, es * n);
+    if (r != hipSuccess) return r;
+    if (es == 8) return hipMemcpy(*dst, src, es * n, hipMemcpyHostToDevice);
+    f32.assign(src, src + n);
+    return hipMemcpy(*dst, f32.data(), es * n, hipMemcpyHostToDevice);
+  };
+  if ((e = upload(&pl->d_x, mean, nm)) != hipSuccess || (e = upload(&pl->d_y, prec, np)) != hipSuccess ||
+      (e = upload(&pl->d_mu, c, (size_t)M)) != hipSuccess)
+    return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  m.x = pl->d_x;
+  m.y = pl->d_y;
+  m.mu = pl->d_mu;
   *out = pl;
   return EY_OK;
 }
@@ -183,6 +290,7 @@ static bool prefer_large(const ey_plan* pl) {
   return w >= (pl->dtype == EY_F32 ? 560 : 200);
 }
 static bool use_large(const ey_plan* pl, int nvec = 3, uint32_t flags = 0) {
+  if (is_mix(pl)) return false;  // a mixture plan has one family: the generic kernels on TargetMix
   if (ey_large_needed(pl, nvec)) return true;
   if (flags & EY_FORCE_GENERIC) return false;
   if (EY_VBIT(4) && !pl->mfma32_ok) return true;
@@ -192,19 +300,19 @@ static bool use_large(const ey_plan* pl, int nvec = 3, uint32_t flags = 0) {
 static bool use_fused16(const ey_plan* pl) { return pl->fused16_ok && !use_mfma32(pl) && !EY_VBIT(4); }
 const char* ey_plan_kernel(const ey_plan* pl) {
   if (!pl) return "generic";
+  if (is_mix(pl)) return "dist";
   EyVariantScope vs(pl);
   if (use_mfma32(pl)) return "mfma32";
   if (use_fused16(pl)) return "fused16";
   return use_large(pl) ? "bgemm" : "generic";
 }
 
-static size_t esize(const ey_plan* pl) { return pl->dtype == EY_F32 ? 4 : 8; }
-
 // Asynchronous on `stream` (a sampler calls this once per minibatch, eeyore/samplers/serial_sampler.py:41-46): the
 // plan's copies of the batch are written by device-to-device copies and two small kernels ordered on the stream; the
 // buffers only grow, so the only synchronisation is the reallocation when a batch is larger than any before it.
 int ey_plan_set_data(ey_plan* pl, const void* x, const void* y, int64_t N, void* stream) {
   if (!pl || !x || !y) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: null argument");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: a mixture plan takes no data (its tables are fixed at creation)");
   if (N < 1 || N > (1 << 24)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: N out of range");
   hipStream_t s = (hipStream_t)stream;
   EY_HIP(hipSetDevice(pl->device));
@@ -246,6 +354,7 @@ int ey_plan_set_data(ey_plan* pl, const void* x, const void* y, int64_t N, void*
 
 int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stream) {
   if (!pl || !mu || !sigma) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_prior: null argument");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_prior: a mixture plan has no prior (the density is the target)");
   hipStream_t s = (hipStream_t)stream;
   EY_HIP(hipSetDevice(pl->device));
   EyModel& m = pl->m;
@@ -357,6 +466,7 @@ int ey_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, v
 }
 
 int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, void* stream) {
+  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: a mixture plan has no data rows");
   int rc = check_ready(pl, C, "ey_log_lik_rows");
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
@@ -793,6 +903,8 @@ int ey_gibbs_table_destroy(ey_gibbs_table* tb) {
 static int gibbs_impl(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                       void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
+  if (pl && is_mix(pl))
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": Gibbs blocks are the nodes of an MLP; a mixture plan has none");
   int rc = check_ready(pl, C, who);
   if (rc < 0) return rc;
   if (!tb) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null block table");
@@ -1092,6 +1204,9 @@ extern "C" int ey_plan_attach_da(ey_plan* pl, void* state, void* step_vec, const
     pl->da_n = pl->da_done = pl->da_C = 0;
     return EY_OK;
   }
+  if (is_mix(pl))
+    EY_FAIL(EY_ERR_UNSUPPORTED, "ey_plan_attach_da: in-kernel dual averaging needs one of the fused kernel families; "
+                                "adapt on the host for a mixture plan");
   if (!step_vec || !table || n <= 0 || C <= 0)
     EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_da: state, step_vec, table, n > 0 and C > 0 are required");
   if (!(d > 0.0 && d < 1.0)) EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_da: the target acceptance must lie in (0, 1)");

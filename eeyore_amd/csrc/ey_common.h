@@ -9,6 +9,10 @@
 
 #define EY_MAX_LAYERS 8
 #define EY_VERSION 200  // 0.2.0
+#define EY_KIND_MLP 0
+#define EY_KIND_MIX 1
+#define EY_MIX_MAX_P 128  // RAM's and AM's limit: lane i owns rows i and i + 64
+#define EY_MIX_MAX_M 16
 
 // ----------------------------------------------------------------------------------------------- errors
 void ey_set_error(const std::string& msg);
@@ -40,11 +44,12 @@ struct EyModel {
   int dmax;                      // max d_l
   int lik;
   int P;
-  int N;
-  const void* x;        // [N, d0]
-  const void* y;        // [N, dK]
+  int N;                // data rows; EY_KIND_MIX: the number of components M
+  int kind;             // EY_KIND_MLP, or EY_KIND_MIX: a Gaussian mixture on theta itself (ey_plan_create_mixture)
+  const void* x;        // [N, d0]; EY_KIND_MIX: mean [M, P]
+  const void* y;        // [N, dK]; EY_KIND_MIX: prec [M, P, P], row-major, symmetric
   const int* labels;    // [N] argmax(y,1) (CE)
-  const void* mu;       // [P]
+  const void* mu;       // [P]; EY_KIND_MIX: c [M]
   const void* inv_var;  // [P] 1/sigma^2
   double prior_const;   // sum_i (-log sigma_i - 0.5 log 2pi)
 };
@@ -165,6 +170,7 @@ int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, flo
 // generic kernels (ey_generic.hip)
 int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                           void* target, void* grad, hipStream_t s);
+void ey_generic_mix_scratch(EyModel& m);  // hrows / dmax of an EY_KIND_MIX model: the evaluation scratch of mix_target
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
                    const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,

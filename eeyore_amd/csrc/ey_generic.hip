@@ -15,6 +15,7 @@
 // the input gradient is row-parallel again.  Tile columns use a stride of 65 elements so that the
 // parameter-parallel reads (different rows j, same column n) hit different LDS banks.
 #include <atomic>
+#include <type_traits>
 
 #include "ey_common.h"
 
@@ -179,6 +180,12 @@ struct TinyFix {
   static constexpr bool on = true;
   static __device__ __forceinline__ constexpr int nl(const EyModel&) { return NL; }
   static __device__ __forceinline__ constexpr int dim(const EyModel&, int k) { return k == 0 ? D0 : (k == 1 ? D1 : (k == 2 ? D2 : D3)); }
+};
+
+// A target that is no MLP: a Gaussian mixture on theta itself (EY_KIND_MIX, mix_target below).  One wave per chain, no
+// row-wave form (on = false).
+struct TargetMix {
+  static constexpr bool on = false;
 };
 
 template <int CTRL, int ROWMASK, typename T>
@@ -434,9 +441,101 @@ __device__ inline void fill_normals(T* dst, const EyRng& rn, int P) {
   __syncthreads();
 }
 
+// ------------------------------------------------------------------ Gaussian-mixture target (EY_KIND_MIX)
+// The densities of the reference's distribution examples (eeyore/models/distribution_model.py:20-28 with a closure that is
+// a multivariate normal or a mixture of them), in closed form:
+//   d_k = theta - mu_k,  v_k = Lambda_k d_k,  a_k = c_k - q_k / 2 with q_k = d_k . v_k,  A = max_k a_k,  s = sum_k exp(a_k - A)
+//   log p = A + log s,   grad log p = -(sum_k exp(a_k - A) v_k) / s
+// Tables shared by all chains in global memory: mean [M, P] (m.x), prec [M, P, P] (m.y), c [M] (m.mu); M = m.N.  Lane i
+// owns rows i and i + 64 of Lambda_k d_k and reads COLUMN i of the exactly symmetric Lambda_k, so that the 64 lanes read
+// consecutive addresses; d_k is broadcast from LDS.  The scratch (the act region, sized by ey_generic_mix_scratch) keeps the
+// M vectors v_k for the gradient pass, d_k, a_k and exp(a_k - A).  M = 1 takes no exp / log: value a_0, gradient -v_0.  The
+// maximum propagates a NaN (fmax would drop it), and a_k = -inf for every k gives exp(NaN): a NaN target either way.
+template <typename T, bool GRAD>
+__device__ T mix_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
+                        T* prior_out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int P = m.P, M = m.N;
+  const T* mean = static_cast<const T*>(m.x);
+  const T* prec = static_cast<const T*>(m.y);
+  const T* cc = static_cast<const T*>(m.mu);
+  T* v = l.act;       // [M][P]
+  T* dd = v + M * P;  // [P]
+  T* aa = dd + P;     // [M]
+  T* ee = aa + M;     // [M]
+  for (int k = 0; k < M; ++k) {
+    const T* mu = mean + (size_t)k * P;
+    const T* Lk = prec + (size_t)k * P * P;
+    __syncthreads();  // the position written by the caller is visible; the previous component's reads of dd are done
+    EY_LANE_PASS(P, i, on) {
+      (void)on;
+      dd[i] = th[i] - mu[i];
+    }
+    __syncthreads();
+    T q = T(0);
+    EY_LANE_PASS(P, i, on) {
+      const T* col = Lk + i;
+      T acc = T(0);
+#pragma unroll 4
+      for (int j = 0; j < P; ++j) acc += col[(size_t)j * P] * dd[j];
+      v[k * P + i] = acc;
+      q += (on ? dd[i] : T(0)) * acc;
+    }
+    q = wave_sum(q);
+    aa[k] = cc[k] - T(0.5) * q;  // (wave-uniform: every lane stores it)
+  }
+  __syncthreads();
+  T val;
+  if (M == 1) {
+    val = aa[0];
+    if (GRAD) {
+      EY_LANE_PASS(P, i, on) {
+        (void)on;
+        const T g = -v[i];
+        gr[i] = has_temp ? g * temp : g;
+      }
+    }
+  } else {
+    T A = aa[0];
+    for (int k = 1; k < M; ++k) {
+      const T a = aa[k];
+      A = (a > A || a != a) ? a : A;
+    }
+    T s = T(0);
+    for (int k = 0; k < M; ++k) {
+      const T e = Num<T>::exp(aa[k] - A);
+      ee[k] = e;  // (wave-uniform)
+      s += e;
+    }
+    val = A + Num<T>::log(s);
+    if (GRAD) {
+      __syncthreads();
+      EY_LANE_PASS(P, i, on) {
+        (void)on;
+        T g = T(0);
+        for (int k = 0; k < M; ++k) g += ee[k] * v[k * P + i];
+        g = -(g / s);
+        gr[i] = has_temp ? g * temp : g;
+      }
+    }
+  }
+  if (has_temp) val *= temp;
+  if (lik_out) *lik_out = val;
+  if (prior_out) *prior_out = T(0);
+  __syncthreads();
+  return val;
+}
+// the scratch of mix_target in units of the carve: hrows rows of TS elements, no delta ping-pong
+void ey_generic_mix_scratch(EyModel& m) {
+  m.hrows = (m.N * m.P + m.P + 2 * m.N + TS - 1) / TS;
+  m.dmax = 0;
+}
+
 template <typename T, bool GRAD, class TINY = TinyOff>
 __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
                          T* prior_out, T* row_out = nullptr, const RowWaves rw = RowWaves{0, 1, nullptr}) {
+  if constexpr (std::is_same<TINY, TargetMix>::value)
+    return mix_target<T, GRAD>(m, l, th, gr, has_temp, temp, lik_out, prior_out);
   const int lane = threadIdx.x & (WAVE - 1);
   const T* x = static_cast<const T*>(m.x);
   const T* y = static_cast<const T*>(m.y);
@@ -906,7 +1005,7 @@ static int tiny_kind(const ey_plan* pl) {
   return (EY_VBIT(9) || m.N >= 128) ? 1 : 0;
 }
 template <typename F>
-static int tiny_dispatch(const ey_plan* pl, F f) {
+static int tiny_dispatch_mlp(const ey_plan* pl, F f) {
   switch (tiny_kind(pl)) {
     case 1: return f(TinyDyn{});
     case 2: return f(TinyFix<2, 2, 2, 1, 0>{});
@@ -919,6 +1018,17 @@ static int tiny_dispatch(const ey_plan* pl, F f) {
     default: return f(TinyOff{});
   }
 }
+// ... and TargetMix for a mixture plan, in every kernel but k_gibbs (the reference's Gibbs needs MLP node blocks)
+template <typename F>
+static int tiny_dispatch(const ey_plan* pl, F f) {
+  if (pl->m.kind == EY_KIND_MIX) return f(TargetMix{});
+  return tiny_dispatch_mlp(pl, f);
+}
+#define EY_TINY_DISPATCH_MLP(fn, ...)                                                                  \
+  tiny_dispatch_mlp(pl, [&](auto tiny_tag) {                                                           \
+    typedef decltype(tiny_tag) TinyS;                                                                  \
+    return pl->dtype == EY_F32 ? fn<float, TinyS>(__VA_ARGS__) : fn<double, TinyS>(__VA_ARGS__);       \
+  })
 #define EY_TINY_DISPATCH(fn, ...)                                                                      \
   tiny_dispatch(pl, [&](auto tiny_tag) {                                                               \
     typedef decltype(tiny_tag) TinyS;                                                                  \
@@ -971,6 +1081,7 @@ int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int6
 }
 
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s) {
+  if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: this plan has no data rows");
   return EY_TINY_DISPATCH(launch_log_target, pl, theta, temp, C, nullptr, nullptr, nullptr, nullptr, s, rows);
 }
 
@@ -1388,7 +1499,8 @@ int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* t
     EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the model's evaluation image and the block table (" +
                                     std::to_string(ey_generic_gibbs_lds(pl, tb)) +
                                     " bytes) do not fit the 160 KiB LDS of a CU");
-  return EY_TINY_DISPATCH(launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter, chain_offset, accepted,
+  if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the blocks are the nodes of an MLP; this plan has none");
+  return EY_TINY_DISPATCH_MLP(launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter, chain_offset, accepted,
                           log_rate, mom_acc, s, run);
 }
 

@@ -3,3 +3,6 @@ from .mlp import MLP, Hyperparameters
 from . import mlp
 from .logistic_regression import LogisticRegression
 from . import logistic_regression
+from .distribution_model import DistributionModel
+from .targets import NormalMixture, MultivariateNormal
+from . import targets

@@ -110,6 +110,41 @@ class Plan:
         self._moments = None
         self._da_refs = None  # tensors an attached dual averaging points into: alive for as long as it is attached
 
+    @classmethod
+    def mixture(cls, c, mean, prec, dtype, device):
+        """The plan of a Gaussian-mixture target on theta itself (ey_plan_create_mixture): ``c`` [M], ``mean`` [M, P] and
+        ``prec`` [M, P, P] are host arrays of doubles, validated by the library before anything touches the device.  Data
+        and prior are "set" from birth; ``kernel`` is 'dist'."""
+        import numpy as np
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(
+                f"eeyore_amd: the hot path runs on an MI355X through the HIP library; device '{device}' is not a ROCm "
+                "device and there is no CPU fallback")
+        if dtype not in _DT:
+            raise ValueError(f"unsupported dtype {dtype}")
+        c, mean, prec = (np.ascontiguousarray(a, dtype=np.float64) for a in (c, mean, prec))
+        if c.ndim != 1 or mean.ndim != 2 or mean.shape[0] != c.shape[0] or prec.shape != mean.shape + mean.shape[1:]:
+            raise ValueError(f"expected c [M], mean [M, P] and prec [M, P, P], got {c.shape}, {mean.shape}, {prec.shape}")
+        self = cls.__new__(cls)
+        self.dtype = dtype
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        self.dims = None
+        self.handle = ct.c_void_p()
+        dp = ct.POINTER(ct.c_double)
+        L.check(L.lib().ey_plan_create_mixture(ct.byref(self.handle), mean.shape[1], c.shape[0], c.ctypes.data_as(dp),
+                                               mean.ctypes.data_as(dp), prec.ctypes.data_as(dp), _DT[dtype], idx),
+                "ey_plan_create_mixture")
+        P = ct.c_int64()
+        L.check(L.lib().ey_plan_num_params(self.handle, ct.byref(P)), "ey_plan_num_params")
+        self.P, self.M = P.value, int(c.shape[0])
+        self._data_key, self._data_ref = None, (None, None)
+        self._prior_key = None
+        self._moments = None
+        self._da_refs = None
+        return self
+
     def __del__(self):
         try:
             if getattr(self, "handle", None) and self.handle.value:

@@ -27,6 +27,10 @@ class Gibbs(SingleChainSerialSampler):
                  chain=None, rng=None, seed=0, chain_offset=0, temperature=None, mode='intended'):
         if mode not in ('intended', 'reference'):
             raise ValueError(f"Gibbs: mode must be 'intended' or 'reference', got {mode!r}")
+        if not hasattr(model, 'num_par_blocks'):
+            raise NotImplementedError(
+                f"Gibbs: {type(model).__name__} has no parameter blocks (the blocks are the nodes of an MLP); a "
+                "DistributionModel is sampled with HMC, MALA, MetropolisHastings, RAM or AM")
         self.model, self.mode = model, mode
         nb = model.num_par_blocks()
         kw = dict(dtype=model.dtype, device=model.device)

@@ -91,6 +91,20 @@ const char* ey_last_error(void);
  * loss_functions[...] (eeyore/constants/constants.py:15-18).  dims has n_layers+1 entries; bias/act n_layers. */
 int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias, const int* act, int likelihood,
                    int dtype, int device_id);
+/* Replaces DistributionModel.__init__ + log_target (eeyore/models/distribution_model.py:6-28) for the closures the
+ * reference's own examples use: a multivariate normal or a mixture of M of them on theta in R^P,
+ *   log p(theta) = log sum_k exp(c[k] - (theta - mean[k])^T prec[k] (theta - mean[k]) / 2)
+ * (c[k] = log w_k - log det(2 pi Sigma_k) / 2 for the normalised density, log w_k for the kernel alone).  c [M],
+ * mean [M, P], prec [M, P, P] row-major are HOST arrays of doubles, read during the call only and rounded once to the plan's
+ * dtype.  Validated before anything touches the device -- EY_ERR_INVALID: P < 1, M < 1, a non-finite entry, a prec[k] that
+ * is not exactly symmetric or has a diagonal entry that is not > 0; EY_ERR_UNSUPPORTED: P > 128, M > 16.
+ * The plan is born with data and prior "set", ey_plan_kernel says "dist" and ey_plan_num_params P.  It serves
+ * ey_log_target (log_lik = the tempered log-density, log_prior = 0), ey_log_target_grad, ey_hmc_*, ey_mala_*, ey_mh_*,
+ * ey_ram_*, ey_am_* and ey_plan_attach_moments with their usual array semantics; ey_plan_set_data / _set_prior return
+ * EY_ERR_INVALID, ey_log_lik_rows, ey_gibbs_* and ey_plan_attach_da EY_ERR_UNSUPPORTED; EY_FORCE_GENERIC, the options and
+ * the variant switches are accepted and change nothing. */
+int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, const double* mean, const double* prec,
+                           int dtype, int device_id);
 int ey_plan_destroy(ey_plan* plan);
 /* Model.num_params (eeyore/models/model.py:34-36) */
 int ey_plan_num_params(const ey_plan* plan, int64_t* P);
@@ -98,7 +112,7 @@ int ey_plan_num_params(const ey_plan* plan, int64_t* P);
  * (fused 16x16x4 trajectory, f32 and f64: one or two hidden layers of at most 64 units (32 in f64), at most 16 inputs,
  * CE-sum on at most 16 logits or BCE-sum on at most 4 sigmoid outputs, every layer with or without a bias), "bgemm"
  * (layerwise batched GEMMs for models beyond LDS and for wide ones that fit, f32 and f64) or "generic" (anything mlp.py
- * builds) */
+ * builds); "dist" for a plan of ey_plan_create_mixture */
 const char* ey_plan_kernel(const ey_plan* plan);
 int ey_plan_set_option(ey_plan* plan, int option, int value);
 int ey_plan_get_option(const ey_plan* plan, int option, int* value);
