@@ -68,6 +68,9 @@ SYMBOLS = {
     "ey_inse_univariate": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "ey_plan_attach_da": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _i]),
     "ey_inse_multivariate": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ey_kernel_pair_sums": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, ct.POINTER(_d),
+                                 ct.POINTER(_i64), ct.POINTER(_i64), _i64, _i, _vp, _vp, _vp, _vp]),
+    "ey_debug_mmd_last_split": (_i, []),
     "ey_debug_set_variant": (_i, [_i]),
     "ey_plan_set_variant": (_i, [_vp, _i]),
     "ey_plan_set_option": (_i, [_vp, _i, _i]),

@@ -114,6 +114,15 @@ class ChainBuffer(Chain):
         from eeyore_amd.stats import batched
         return batched.mc_se(self.get_samples())
 
+    def mmd(self, x2, kernel=None, lengths=None, lengths2=None):
+        """Maximum mean discrepancy of every chain against the sample ``x2`` ([m, P], e.g. a direct sample of the target, or
+        [m, C, P]) under ``kernel`` (default ``IsoSEKernel()``), [C]; with ``lengths`` the curve against the number of draws,
+        [k, C] (one device pass, stats.batched.mmd_chains)."""
+        from eeyore_amd.kernels import IsoSEKernel
+        from eeyore_amd.stats import batched
+        return batched.mmd_chains(self.get_samples(), x2, IsoSEKernel() if kernel is None else kernel, lengths=lengths,
+                                  lengths2=lengths2)
+
     def acceptance_rate(self):
         """Per-chain acceptance [C] = sum(accepted) / num_samples (chain_list.py:94-96); [C, S], per sub-step, when the
         sampler stores S flags per draw (Gibbs)."""

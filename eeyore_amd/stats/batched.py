@@ -180,3 +180,65 @@ def multi_ess_chains(x):
     xc = x - x.mean(1, keepdim=True)
     cov = torch.matmul(xc.transpose(1, 2), xc) / (n - 1)                 # eeyore/stats/cov.py:5-15
     return n * (torch.linalg.det(cov) / torch.linalg.det(inse_mc_cov_chains(x))) ** (1.0 / p)
+
+
+# ---------------------------------------------------------------------------------------------- discrepancy, many chains
+def _check_lengths(name, lengths, n, biased):
+    vals = [int(v) for v in lengths]
+    if not vals:
+        raise ValueError(f"{name} must not be empty")
+    if any(v < 1 or v > n for v in vals):
+        raise ValueError(f"{name} must lie in [1, {n}]")
+    if any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{name} must be non-decreasing")
+    if not biased and vals[0] < 2:
+        raise ValueError(f"biased=False needs {name} >= 2")
+    return vals
+
+
+def mmd_chains(samples, x2, kernel, lengths=None, lengths2=None, biased=True, layout="ncp", squared=False):
+    """The reference's mmd (eeyore/stats/discrepancy.py:3-19) of every chain of a stored run against a second sample, in one
+    device pass (``ey_kernel_pair_sums``: no [n, n] matrix, f64 arithmetic for f32 and f64 samples alike).
+    ``samples``: [n, C, p] as a chain buffer stores a run (``layout="ncp"``) or [C, n, p] (``"cnp"``).  ``x2``: [m, p], one
+    sample for all chains (a direct sample of the target), or one per chain, [m, C, p] / [C, m, p] following ``layout``.
+    ``kernel``: an IsoSEKernel, RQKernel or PeriodicKernel.  ``lengths``: k non-decreasing numbers of draws -> the statistic
+    of each chain's first lengths[t] draws, [k, C]; ``lengths2`` the rows of x2 each is compared with (None: all of x2;
+    ``lengths2=lengths`` is the curve of the reference's examples).  Without ``lengths``: [C], the whole run.
+    ``biased=False``: the unbiased estimate of the squared statistic, which can be negative (ask for it with
+    ``squared=True``).  Returns f64 on the device: mmd, or its square with ``squared=True``.  As in the reference the square
+    root is not clamped: rounding can make it NaN where the two samples coincide."""
+    from eeyore_amd.kernels.homogeneous import HomogeneousKernel, pair_sums
+    if not isinstance(kernel, HomogeneousKernel) or kernel.device_kind() is None:
+        raise ValueError("mmd_chains: the kernel must be an IsoSEKernel, RQKernel or PeriodicKernel")
+    if not torch.is_tensor(samples) or not torch.is_tensor(x2) or samples.dim() != 3 or x2.dim() not in (2, 3):
+        raise ValueError("mmd_chains: samples must be a 3-d tensor and x2 a 2-d or 3-d tensor")
+    if layout not in ("ncp", "cnp"):
+        raise ValueError("layout must be 'ncp' or 'cnp'")
+    if samples.dtype not in _DT or x2.dtype != samples.dtype:
+        raise ValueError("mmd_chains: samples and x2 must share one dtype, float32 or float64")
+    n, C = (samples.shape[0], samples.shape[1]) if layout == "ncp" else (samples.shape[1], samples.shape[0])
+    if x2.shape[-1] != samples.shape[-1]:
+        raise ValueError("mmd_chains: samples and x2 differ in p")
+    if x2.dim() == 3 and (x2.shape[1] if layout == "ncp" else x2.shape[0]) != C:
+        raise ValueError("mmd_chains: a per-chain x2 must have the samples' number of chains")
+    m = x2.shape[0] if x2.dim() == 2 or layout == "ncp" else x2.shape[1]
+    if lengths is None:
+        if lengths2 is not None:
+            raise ValueError("mmd_chains: lengths2 needs lengths")
+        l1, l2 = _check_lengths("n", [n], n, biased), _check_lengths("m", [m], m, biased)
+    else:
+        l1 = _check_lengths("lengths", lengths, n, biased)
+        l2 = _check_lengths("lengths2", lengths2 if lengths2 is not None else [m] * len(l1), m, biased)
+        if len(l2) != len(l1):
+            raise ValueError("mmd_chains: lengths and lengths2 differ in length")
+    if min(n, m, C, samples.shape[-1]) < 1:
+        raise ValueError("mmd_chains: empty input")
+    if not samples.is_cuda or not x2.is_cuda:
+        raise RuntimeError("eeyore_amd.stats.batched: the samples must be on the ROCm device (no CPU fallback)")
+    s11, s22, s12 = pair_sums(samples, x2, kernel, layout=layout, lengths=None if lengths is None else l1,
+                              lengths2=None if lengths is None else l2, include_diag=biased)
+    a = torch.tensor(l1, dtype=torch.float64, device=samples.device)
+    b = torch.tensor(l2, dtype=torch.float64, device=samples.device)
+    sq = s11 / (a * a if biased else a * (a - 1)) + s22 / (b * b if biased else b * (b - 1)) - 2 * s12 / (a * b)   # [C, k]
+    out = sq if squared else torch.sqrt(sq)
+    return out[:, 0] if lengths is None else out.T.contiguous()

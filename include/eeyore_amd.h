@@ -346,6 +346,37 @@ int ey_inse_univariate(const void* x, int64_t n, int64_t S, int dtype, void* sig
 int ey_inse_multivariate(const void* x, int64_t n, int64_t C, int64_t p, int64_t stride_n, int64_t stride_c, int dtype,
                          void* sig, void* cov, void* mean, void* num_pairs, void* stream);
 
+/* Sums of a homogeneous kernel function over pairs of samples, for C chains and k prefix lengths in one pass: what the
+ * reference's Kernel.sum_symm_K / Kernel.sum_K compute with one Python call per pair (eeyore/kernels/kernel.py:64-101), and
+ * all that squared_mmd / mmd need (eeyore/stats/discrepancy.py:3-19).  x1 is addressed as x1[i * stride1_n + c * stride1_c + j]
+ * (elements; i < n1, c < C, j < p) as in ey_inse_multivariate, x2 likewise with n2 rows; stride2_c = 0: one x2 for all chains
+ * (its own sum is then computed once and written to every chain's row).  For chain c and prefix t:
+ *   s11[c,t] = sum_symm_K(x1_c[:len1[t]], include_diag)   s22[c,t] = sum_symm_K(x2_c[:len2[t]], include_diag)
+ *   s12[c,t] = sum_K(x1_c[:len1[t]], x2_c[:len2[t]])      (each [C,k] double on the device, all three required)
+ * kind / params (HOST doubles): 0 IsoSE {scale, l}: scale exp(-d2 / (2 l)) (iso_se_kernel.py:12-13); 1 RQ {scale, l, a}:
+ * scale (1 + d2 / (2 a l))^-a (rq_kernel.py:13-14); 2 Periodic {scale, l, p}: scale exp(-2 sin^2(d / p) / l)
+ * (periodic_kernel.py:13-14), with d2 = sum_j (a_j - b_j)^2 in the difference form and d = sqrt(d2).  Samples are f32 or f64
+ * (`dtype`); arithmetic and sums are f64 for both (an f32 sample is exact in f64; the reference's f32 result is a sequential
+ * f32 sum and is not imitated).  len1, len2: HOST arrays of k non-decreasing lengths in [1, n1] / [1, n2], read during the
+ * call (with k > 1 the call waits for `stream` once, until they have been copied); both NULL with k = 1: the full lengths.
+ * Symmetric sums count a pair below the diagonal twice and add the diagonal when include_diag != 0.  No floating-point
+ * atomics: the same call gives the same bits, and so do two chains with the same data in one call.  Where there are few
+ * chains their tiles are split over several workgroups, whose partial sums go through a workspace the call allocates and
+ * frees on the stream and are added in a fixed order (4 workgroups per CU are aimed at; EY_MMD_SPLIT_TARGET in the
+ * environment, read at every call, replaces that number).  Non-finite samples are not checked: they make that chain's
+ * sums NaN and no other chain's.  EY_ERR_INVALID, before anything touches the device: n1, n2, C, p or k < 1; unknown kind or
+ * dtype; scale, l or a not finite and > 0; Periodic p not finite or 0; exactly one of len1 / len2 NULL (or both with
+ * k > 1); lengths decreasing or outside [1, n]; include_diag = 0 with a length < 2; a NULL pointer.  EY_ERR_UNSUPPORTED:
+ * k > 1024; p > 2^31 - 17; more than 2^24 - 1 workgroups in one launch (C times the workgroups per chain: C > 16777215). */
+int ey_kernel_pair_sums(const void* x1, int64_t n1, int64_t C, int64_t p, int64_t stride1_n, int64_t stride1_c,
+                        const void* x2, int64_t n2, int64_t stride2_n, int64_t stride2_c, int dtype, int kind,
+                        const double* params, const int64_t* len1, const int64_t* len2, int64_t k, int include_diag,
+                        void* s11, void* s22, void* s12, void* stream);
+
+/* Diagnostic (not part of the drop-in surface): the workgroups per chain of the launch that computed s11 / s12 in this
+ * thread's last ey_kernel_pair_sums call that reached the device: 1 = every chain in one workgroup, > 1 = the split route. */
+int ey_debug_mmd_last_split(void);
+
 /* Attach running-moment accumulators to a plan: from now on every ey_hmc_step / ey_mala_step / ey_mh_step on it also
  * performs, for the state each chain is left in, exactly what ey_stats_update does (s1 += theta, s2 += theta^2,
  * acc += accepted) -- inside the fused kernel where there is one (no extra pass over [C,P]), as a trailing pass on
