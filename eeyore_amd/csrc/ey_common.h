@@ -189,6 +189,11 @@ size_t ey_generic_ram_lds(const ey_plan* pl);  // dynamic LDS of one chain's wor
 int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                    void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+// MH with a fixed lower-triangular proposal factor (k_mh_tril): as RAM, whatever plan.kernel says
+size_t ey_generic_mh_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
+int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                       const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
 // adaptive Metropolis (k_am): the state and the settings of AM.draw beside theta and target, whatever plan.kernel says
 struct EyAm {

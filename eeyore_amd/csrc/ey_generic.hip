@@ -1370,6 +1370,126 @@ int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const voi
                           log_rate, s, run);
 }
 
+// ----------------------------------------------------------------------------------------------- MH with a fixed factor
+// MetropolisHastings.draw (eeyore/samplers/metropolis_hastings.py:41-73) whose kernel is a MultivariateNormalKernel: the
+// proposal MultivariateNormal(theta, scale_tril = L).sample() = theta + L z, the loop body of k_mh otherwise (the same
+// Philox streams and fill_normals, so L = I proposes what k_mh does with scale = 1).  k_ram without its adaptation: one
+// wave per chain, lane <-> rows lane and lane + 64 (P <= 128), the chain's factor staged ONCE per launch into LDS behind
+// the MH image in ram_col order, the proposal k_ram's column sweep with one running sum per row.
+// tril [G, P, P] row-major: G == 1 one factor for all chains, tril_index == NULL (G == C) chain c's own, otherwise factor
+// tril_index[c], clamped into [0, G) so that a bad index cannot become an out-of-bounds read (the range is the caller's
+// to check).  Only j <= i of a factor is read.
+// z waits in the image's gradient slot, which a gradient-free evaluation leaves free until the proposal is made.
+__host__ __device__ static size_t mh_tril_extra_bytes(int P, size_t esz) {
+  return esz * (((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3);  // the packed factor
+}
+
+template <typename T, class TINY>
+__global__ void __launch_bounds__(WAVE) k_mh_tril(EyModel m, T* theta, T* target, const T* tril, int64_t G,
+                                                  const int* tril_index, const T* z_in, const T* u_in, const T* temp,
+                                                  uint64_t seed, uint64_t iter0, uint64_t chain_offset,
+                                                  unsigned char* accepted, T* log_rate_o, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, 2);
+  const int P = m.P;
+  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 2, sizeof(T)));
+  T* w = l.gr;
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c);
+  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
+  const T* Lg = tril + g * (int64_t)P * P;
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Lg[(int64_t)i * P + j];
+  T t_state = target[c];
+  for (int it = 0; it < run.n_iters; ++it) {  // ey_mh_tril_run: see k_mala
+    const uint64_t iter = iter0 + (uint64_t)it;
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    if (!z_in) fill_normals<T>(w, rn, P);
+    else {
+      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
+      __syncthreads();
+    }
+    // theta + L z: k_ram's column sweep (clamped index, the term's input selected to zero: DESIGN.md 4.4)
+    T acc[2] = {T(0), T(0)};
+    for (int j = 0; j < P; ++j) {
+      const T zj = w[j];
+      const T* col = S + ram_col(j, P) - j;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int i = lane + r * WAVE;
+        const bool on = i >= j && i < P;
+        const T s = col[on ? i : j];
+        acc[r] += (on ? s : T(0)) * zj;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      if (i < P) l.th[i] = theta[c * P + i] + acc[r];
+    }
+    __syncthreads();
+    const T tv = eval_target<T, false, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
+    const T log_rate = tv - t_state;  // symmetric kernel (metropolis_hastings.py:50)
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    const T u = u_in ? u_in[c] : ey_rng_uniform<T>(ru);
+    const bool acc_ = Num<T>::log(u) < log_rate;  // :56
+    if (acc_) {
+      t_state = tv;
+      for (int i = lane; i < P; i += WAVE) theta[c * P + i] = l.th[i];
+    }
+    if (run.samples) {
+      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
+      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? l.th[i] : theta[c * P + i];
+    }
+    if (lane == 0) {
+      if (acc_) target[c] = tv;
+      accepted[c] = acc_ ? 1 : 0;
+      if (log_rate_o) log_rate_o[c] = log_rate;
+      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
+      if (run.accept_count && acc_) run.accept_count[c] += 1;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, class TINY>
+static int launch_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                          const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                          uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
+  const size_t bytes = ey_generic_mh_tril_lds(pl);
+  int rc;
+  if ((rc = prep(k_mh_tril<T, TINY>, bytes))) return rc;
+  hipLaunchKernelGGL((k_mh_tril<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
+                     (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (const T*)temp, seed, iter,
+                     chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : one, C);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+
+size_t ey_generic_mh_tril_lds(const ey_plan* pl) {
+  const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
+  return lds_bytes(pl->m, 2, esz) + mh_tril_extra_bytes(pl->m.P, esz);
+}
+
+int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                       const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  if (pl->m.P > RAM_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "MH with a factor: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
+                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
+  if (ey_generic_mh_tril_lds(pl) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "MH with a factor: the factor and the model's evaluation image (" +
+                                    std::to_string(ey_generic_mh_tril_lds(pl)) +
+                                    " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_TINY_DISPATCH(launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, temp, C, seed, iter, chain_offset,
+                          accepted, log_rate, s, run);
+}
+
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
 // Gibbs.draw (eeyore/samplers/gibbs.py:67-102): per draw, S accept/reject sub-steps, each a Normal random-walk proposal
 // for one block of parameters and one evaluation of the whole log-target.  The kernel knows nothing of nodes: it walks a

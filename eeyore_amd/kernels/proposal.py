@@ -2,10 +2,11 @@
 eeyore/kernels/{kernel,normalized_kernel,normal_kernel}.py).
 
 Inside the samplers the proposal draw and its log-density are part of the fused HIP step (``ey_mala_step`` /
-``ey_mh_step``); a ``NormalKernel`` object is how a script hands the proposal scale to ``MetropolisHastings`` and how
-it can inspect or evaluate the proposal density of the current state."""
+``ey_mh_step`` / ``ey_mh_tril_step``); a ``NormalKernel`` or ``MultivariateNormalKernel`` object is how a script hands the
+proposal scale or factor to ``MetropolisHastings`` and how it can inspect or evaluate the proposal density of the current
+state."""
 import torch
-from torch.distributions import Normal
+from torch.distributions import MultivariateNormal, Normal
 
 
 class Kernel:
@@ -137,4 +138,51 @@ class NormalKernel(NormalizedKernel):
     def k(self, x1, x2, scale=None):
         """Density of x1 under the kernel centred at x2."""
         self.set_density_params(x2, scale=scale)
+        return torch.exp(self.log_prob(x1))
+
+
+def check_scale_tril(t, P):
+    """Refuse a proposal factor that ``ey_mh_tril_step`` cannot use: ``t`` must be a ``[P, P]`` or ``[G, P, P]`` tensor
+    whose lower triangles are finite with a positive diagonal (the strict upper triangle is never read)."""
+    if not torch.is_tensor(t) or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (P, P) or t.shape[0] < 1:
+        shape = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"scale_tril must be a [{P}, {P}] or [G, {P}, {P}] tensor, got {shape}")
+    if not bool(torch.isfinite(torch.tril(t)).all()):
+        raise ValueError("scale_tril has a non-finite entry in its lower triangle")
+    if not bool((torch.diagonal(t, dim1=-2, dim2=-1) > 0).all()):
+        raise ValueError("scale_tril must have a positive diagonal")
+
+
+class MultivariateNormalKernel(NormalizedKernel):
+    """N(loc, L L^T) with the lower-triangular factor ``scale_tril`` = L (eeyore/kernels/multivariate_normal_kernel.py).
+    ``scale_tril`` keeps the factor as it was given, ``[P, P]`` or ``[C, P, P]``: a batched ``loc`` makes torch broadcast
+    the density's own copy, and ``MetropolisHastings`` must see the caller's shape."""
+
+    def __init__(self, loc, scale_tril):
+        self.set_density(loc, scale_tril)
+
+    @property
+    def scale_tril(self):
+        return self._scale_tril
+
+    def set_density(self, loc, scale_tril):
+        self._scale_tril = scale_tril
+        self.density = MultivariateNormal(loc, scale_tril=scale_tril)
+
+    def set_density_params(self, loc, scale_tril=None):
+        """Re-centre the density; a new factor rebuilds it (assigning ``density.scale_tril``, as the reference does,
+        changes nothing ``rsample`` reads)."""
+        if scale_tril is not None:
+            self.set_density(loc, scale_tril)
+        elif loc.shape != self.density.loc.shape:  # another batch of chains: the batch shape is fixed at construction
+            self.set_density(loc, self._scale_tril)
+        else:
+            self.density.loc = loc
+
+    def log_prob(self, state):
+        return self.density.log_prob(state).sum()
+
+    def k(self, x1, x2, scale_tril=None):
+        """Density of x1 under the kernel centred at x2."""
+        self.set_density_params(x2, scale_tril=scale_tril)
         return torch.exp(self.log_prob(x1))

@@ -424,6 +424,63 @@ class Plan:
         self._stepped()
         return out
 
+    def _tril(self, tril, index, C):
+        """(G, index) of a proposal factor ``tril`` ([P, P] or [G, P, P]) for C chains, checked: without ``index`` G is 1
+        or C, with it ``index`` is an int32 [C] tensor on the device with every entry in [0, G)."""
+        if (not torch.is_tensor(tril) or tril.device != self.device or tril.dtype != self.dtype
+                or not tril.is_contiguous() or tril.dim() not in (2, 3) or tuple(tril.shape[-2:]) != (self.P, self.P)
+                or tril.shape[0] < 1):
+            raise ValueError(f"tril must be a contiguous [{self.P}, {self.P}] or [G, {self.P}, {self.P}] tensor of the "
+                             "plan's dtype on its device")
+        G = 1 if tril.dim() == 2 else int(tril.shape[0])
+        if index is None:
+            if G not in (1, C):
+                raise ValueError(f"tril holds {G} factors for {C} chains: without index it must hold 1 or {C}")
+            return G, None
+        if (not torch.is_tensor(index) or index.device != self.device or index.dtype != torch.int32
+                or tuple(index.shape) != (C,) or not index.is_contiguous()):
+            raise ValueError(f"index must be a contiguous int32 tensor of shape ({C},) on the plan's device")
+        key = (index.data_ptr(), index._version, G, C)  # the range check reads the device: once per index, not per draw
+        if C and getattr(self, "_tril_index_checked", None) != key:
+            if int(index.min()) < 0 or int(index.max()) >= G:
+                raise ValueError(f"index must lie in [0, {G})")
+            self._tril_index_checked = key
+        return G, index
+
+    def mh_tril_step(self, theta, target, tril, index=None, z=None, u=None, temp=None, seed=0, it=0, chain_offset=0,
+                     flags=0, out=None):
+        """One MetropolisHastings.draw of every chain with the proposal theta + L z (ey_mh_tril_step): ``tril`` is one
+        lower-triangular factor [P, P] for all chains, one per chain [C, P, P], or [G, P, P] with ``index`` [C] int32
+        naming each chain's factor.  Only the lower triangle is read."""
+        C = self._theta(theta)
+        G, index = self._tril(tril, index, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
+        temp, u = self._opt(temp, C), self._opt(u, C)
+        L.check(L.lib().ey_mh_tril_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index), L.ptr(z),
+                                        L.ptr(u), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
+                                        L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)),
+                "ey_mh_tril_step")
+        self._stepped()
+        return out
+
+    def mh_tril_run(self, theta, target, tril, n_iters, index=None, temp=None, seed=0, it=0, chain_offset=0, flags=0,
+                    samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
+        """``n_iters`` iterations of ``mh_tril_step`` in one launch (ey_mh_tril_run); records as in ``hmc_run``."""
+        C = self._theta(theta)
+        G, index = self._tril(tril, index, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8))
+        temp = self._opt(temp, C)
+        n_iters = int(n_iters)
+        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
+        L.check(L.lib().ey_mh_tril_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index),
+                                       L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
+                                       L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
+                                       L.ptr(out["accepted"]), _stream(self.device)), "ey_mh_tril_run")
+        self._stepped(n_iters)
+        return out
+
     def _chol(self, chol, C):
         if (chol.device != self.device or chol.dtype != self.dtype or not chol.is_contiguous()
                 or tuple(chol.shape) != (C, self.P, self.P)):

@@ -11,6 +11,7 @@ from .metropolis_hastings import MetropolisHastings
 from .base import SerialSampler
 from eeyore_amd.chains import ChainBuffer, ChainBufferView, ChainFile
 from eeyore_amd.datasets import DataCounter
+from eeyore_amd.kernels import MultivariateNormalKernel
 
 
 def pt_segments(idx, num_iters, num_burnin_iters, between_step, fused_block):
@@ -36,6 +37,9 @@ class PowerPosteriorSampler(SerialSampler):
 
     ``samplers`` is the reference's list ``[[name, kwargs], ...]``, one entry per temperature; ``name`` is 'MALA' or
     'MetropolisHastings' as in the reference (:71-82), or 'HMC' (an extension the reference does not offer).  All
+    With 'MetropolisHastings' the kwargs of the temperatures may each hold a ``MultivariateNormalKernel`` with a ``[P, P]``
+    ``scale_tril``: every temperature then proposes with its own factor (the identity where none is given), which stays with
+    the temperature when a between-chain move exchanges states.  ``NormalKernel``s are still taken from temperature 0.  All
     temperatures are advanced by ONE fused step: the K x R chains (K temperatures, R independent replicas of the whole
     ladder; ``theta0`` of shape [P] gives R = 1, [R, P] gives R ladders) form one chain batch whose per-chain
     temperature vector goes to the HIP kernel (temperature multiplies log-likelihood and log-prior,
@@ -103,9 +107,26 @@ class PowerPosteriorSampler(SerialSampler):
                 raise ValueError("num_steps must be the same at every temperature")
             self.sampler = HMC(model, step=per_chain('step', 0.1), num_steps=ns.pop(), **common)
         elif name == 'MetropolisHastings':
-            self.sampler = MetropolisHastings(model, **common)
-            if any('kernel' in k for k in kw):
-                self.sampler.kernel = kw[0]['kernel']
+            kernels = [k.get('kernel') for k in kw]
+            mvn = [isinstance(k, MultivariateNormalKernel) for k in kernels]
+            if any(mvn):
+                # one factor per temperature: K factors on the device, state row k * R + r proposes with factor k
+                P = model.num_params()
+                if any(k is not None and not m for k, m in zip(kernels, mvn)):
+                    raise ValueError("the temperatures' kernels must be all NormalKernels or all MultivariateNormalKernels "
+                                     "(a temperature without a kernel proposes with the identity factor)")
+                if any(m and tuple(k.scale_tril.shape) != (P, P) for k, m in zip(kernels, mvn)):
+                    raise ValueError(f"a temperature's MultivariateNormalKernel must hold one [{P}, {P}] scale_tril")
+                eye = torch.eye(P, dtype=self.dtype, device=self.device)
+                trils = torch.stack([k.scale_tril.detach().to(device=self.device, dtype=self.dtype) if m else eye
+                                     for k, m in zip(kernels, mvn)])
+                self.sampler = MetropolisHastings(model, **common)
+                self.sampler._set_tril(trils, index=torch.arange(K, dtype=torch.int32).repeat_interleave(R))
+                self.sampler.kernel = MultivariateNormalKernel(self.sampler.current['sample'], trils[0])
+            else:
+                self.sampler = MetropolisHastings(model, **common)
+                if any('kernel' in k for k in kw):
+                    self.sampler.kernel = kw[0]['kernel']
         else:
             raise ValueError(f"unknown within-chain sampler {name!r}")
         self.chains = [self.init_chain(i, storage, self.keys, Path(path), mode) for i in range(K)]

@@ -100,7 +100,7 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
  * is not exactly symmetric or has a diagonal entry that is not > 0; EY_ERR_UNSUPPORTED: P > 128, M > 16.
  * The plan is born with data and prior "set", ey_plan_kernel says "dist" and ey_plan_num_params P.  It serves
  * ey_log_target (log_lik = the tempered log-density, log_prior = 0), ey_log_target_grad, ey_hmc_*, ey_mala_*, ey_mh_*,
- * ey_ram_*, ey_am_* and ey_plan_attach_moments with their usual array semantics; ey_plan_set_data / _set_prior return
+ * ey_mh_tril_*, ey_ram_*, ey_am_* and ey_plan_attach_moments with their usual array semantics; ey_plan_set_data / _set_prior return
  * EY_ERR_INVALID, ey_log_lik_rows, ey_gibbs_* and ey_plan_attach_da EY_ERR_UNSUPPORTED; EY_FORCE_GENERIC, the options and
  * the variant switches are accepted and change nothing. */
 int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, const double* mean, const double* prec,
@@ -208,6 +208,27 @@ int ey_ram_step(ey_plan* plan, void* theta, void* target, void* chol, const void
 int ey_ram_run(ey_plan* plan, void* theta, void* target, void* chol, double a, double g, uint64_t n, const void* temp,
                int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
                void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream);
+
+/* One MetropolisHastings.draw (eeyore/samplers/metropolis_hastings.py:41-73) whose kernel is a
+ * MultivariateNormalKernel(theta, scale_tril): prop = theta + L z with a FIXED lower-triangular factor L, accept iff
+ * log(u) < log_rate = target(prop) - target(theta).  z [C,P], u [C] replace the random draws (NULL => Philox, the streams
+ * of ey_mh_step: with L = I the proposal is ey_mh_step's with scale = 1).  tril [G,P,P] row-major device array of the
+ * plan's dtype, read only; only the lower triangle (j <= i) of a factor is read, the strict upper triangle may hold
+ * anything.  Which factor a chain uses: G == 1, the one factor; tril_index == NULL, chain c uses factor c (G == C);
+ * otherwise factor tril_index[c] (device int32 [C]), clamped into [0, G) -- checking its range is the caller's business.
+ * EY_ERR_INVALID: a null theta / target / tril / accepted, n_iters < 1, G < 1, tril_index == NULL with G neither 1 nor C.
+ * Served by one kernel for every model (whatever ey_plan_kernel reports), mixture plans included, with P <= 128 whose
+ * factor fits beside its evaluation image in LDS; EY_ERR_UNSUPPORTED otherwise, before any launch and with nothing
+ * written.  flags is accepted and ignored.  log_rate [C] output may be NULL. */
+int ey_mh_tril_step(ey_plan* plan, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                    const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                    uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate, void* stream);
+/* n_iters iterations in one launch (the factor is staged once), records as ey_mh_run; ey_mh_tril_run is bit-identical to
+ * n_iters calls of ey_mh_tril_step with z = u = NULL. */
+int ey_mh_tril_run(ey_plan* plan, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                   const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                   int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
+                   void* stream);
 
 /* The block table of a Gibbs sampler: S sub-steps in visiting order, sub-step s proposing for the parameters
  * blk_idx[blk_off[s] .. blk_off[s+1]) with the Normal scale blk_scale[s].  The table is model-agnostic (blockwise
