@@ -59,6 +59,10 @@ SYMBOLS = {
     "ey_mh_tril_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
     "ey_mh_tril_run": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
                             _vp]),
+    "ey_mala_tril_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp,
+                               _vp, _vp]),
+    "ey_mala_tril_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,
+                              _vp, _vp, _vp, _vp]),
     "ey_am_step": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32,
                         _vp, _vp, _vp, _vp, _vp]),
     "ey_am_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,

@@ -829,6 +829,48 @@ int ey_mh_tril_run(ey_plan* pl, void* theta, void* target, const void* tril, int
                       accepted, nullptr, stream, &run, "ey_mh_tril_run");
 }
 
+// MALA with a fixed factor runs on k_mala_tril (ey_generic.hip) for every model, as MH with one does on k_mh_tril
+static int mala_tril_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                          const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
+                          void* log_rate, void* stream, const EyRun* run, const char* who) {
+  int rc = check_ready(pl, C, who);
+  if (rc) return rc < 0 ? rc : EY_OK;
+  EyVariantScope vs(pl);
+  if (!theta || !target || !grad || !tril || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (!(step > 0.0) && !step_vec) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": step must be positive");
+  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
+  if (G < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the number of factors G must be >= 1");
+  if (!tril_index && G != 1 && G != C)
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": without tril_index, G must be 1 or the number of chains");
+  if (C == 0) return EY_OK;
+  if ((rc = moments_check(pl, C, who))) return rc;
+  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
+  EY_HIP(hipSetDevice(pl->device));
+  rc = ey_generic_mala_tril(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C, seed, iter,
+                            chain_offset, accepted, log_rate, (hipStream_t)stream, run);
+  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+}
+
+int ey_mala_tril_step(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                      const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                      const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                      void* accepted, void* log_rate, void* stream) {
+  (void)flags;
+  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C, seed, iter,
+                        chain_offset, accepted, log_rate, stream, nullptr, "ey_mala_tril_step");
+}
+
+int ey_mala_tril_run(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                     const void* tril_index, double step, const void* step_vec, const void* temp, int64_t C, uint64_t seed,
+                     uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets,
+                     void* accepted_rec, void* accept_count, void* accepted, void* stream) {
+  (void)flags;
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, nullptr, nullptr, step, step_vec, temp, C, seed, iter,
+                        chain_offset, accepted, nullptr, stream, &run, "ey_mala_tril_run");
+}
+
 // AM runs on k_am (ey_generic.hip) for every model, as RAM does on k_ram
 static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
                    uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, void* stream, const EyRun* run,

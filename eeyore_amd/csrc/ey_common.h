@@ -194,6 +194,12 @@ size_t ey_generic_mh_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain's
 int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                        const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                        uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+// MALA with a fixed lower-triangular proposal factor (k_mala_tril): as k_mh_tril, whatever plan.kernel says
+size_t ey_generic_mala_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
+int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                         const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                         const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
+                         void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
 // adaptive Metropolis (k_am): the state and the settings of AM.draw beside theta and target, whatever plan.kernel says
 struct EyAm {

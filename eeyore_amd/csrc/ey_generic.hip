@@ -1490,6 +1490,188 @@ int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril,
                           accepted, log_rate, s, run);
 }
 
+// ----------------------------------------------------------------------------------------------- MALA with a fixed factor
+// MALA.draw (eeyore/samplers/mala.py:46-82) whose kernel is a MultivariateNormalKernel: the proposal
+// MultivariateNormal(loc, scale_tril = L).sample() = loc + L z around loc = theta + step/2 grad, the loop body of k_mala
+// otherwise (the same Philox streams and fill_normals).  step enters the mean only: the covariance is L L^T as given.
+// k_mh_tril's layout: one wave per chain, lane <-> rows lane and lane + 64 (P <= 128), the chain's factor staged ONCE per
+// launch into LDS behind the MALA image in ram_col order, chosen as there (G, tril_index, clamped); only j <= i is read.
+// z waits in the image's slot of the proposal's gradient, which is free until the evaluation at the proposal.
+// The proposal is no longer symmetric:  log_rate = (t' - t) + |L^-1 (prop - loc)|^2 / 2 - |L^-1 (theta - loc')|^2 / 2 with
+// loc' = prop + step/2 grad', the -sum log L_ii - P/2 log 2 pi of both densities cancelling.
+
+// |L^-1 r|^2 for the packed factor S by column-oriented forward substitution: a lane holds the residuals of its two rows
+// (r0: row lane, r1: row lane + 64; rows >= P hold 0 and are never touched), y_j = r_j / L_jj comes from the lane that owns
+// row j (j is wave-uniform) and every lane sums the y_j^2 in the order of j, so the result is wave-uniform.  Clamped
+// index, the term's input selected to zero, no memory operation behind a per-lane branch.
+template <typename T>
+__device__ inline T tril_solve_sq(const T* S, int P, T r0, T r1, int lane) {
+  T q = T(0);
+  for (int j = 0; j < P; ++j) {
+    const T* col = S + ram_col(j, P) - j;
+    const T y = __shfl(j < WAVE ? r0 : r1, j & (WAVE - 1), WAVE) / col[j];
+    q += y * y;
+    {
+      const int i = lane;
+      const bool on = i > j && i < P;
+      const T s = col[on ? i : j];
+      r0 -= (on ? s : T(0)) * y;
+    }
+    {
+      const int i = lane + WAVE;
+      const bool on = i > j && i < P;
+      const T s = col[on ? i : j];
+      r1 -= (on ? s : T(0)) * y;
+    }
+  }
+  return q;
+}
+
+template <typename T, class TINY>
+__global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* target, T* grad, const T* tril, int64_t G,
+                                                    const int* tril_index, const T* z_in, const T* u_in, T step,
+                                                    const T* step_vec, const T* temp, uint64_t seed, uint64_t iter0,
+                                                    uint64_t chain_offset, unsigned char* accepted, T* log_rate_o,
+                                                    EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, 4);
+  const int P = m.P;
+  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 4, sizeof(T)));
+  T* prop = l.a;
+  T* gp = l.b;
+  T* w = l.b;
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  const T eps = step_vec ? step_vec[c] : step;
+  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c);
+  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
+  const T* Lg = tril + g * (int64_t)P * P;
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Lg[(int64_t)i * P + j];
+  T t_state = target[c];
+  for (int it = 0; it < run.n_iters; ++it) {  // ey_mala_tril_run: see k_mala
+    const uint64_t iter = iter0 + (uint64_t)it;
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    if (!z_in) fill_normals<T>(w, rn, P);
+    else {
+      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
+      __syncthreads();
+    }
+    // loc = kernel_mean (mala.py:35-36); a lane without a row repeats row P - 1's loads and stores
+    T loc[2], acc[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      const int ii = i < P ? i : P - 1;
+      const T th = theta[c * P + ii], gi = grad[c * P + ii];
+      l.th[ii] = th;
+      l.gr[ii] = gi;
+      loc[r] = th + T(0.5) * eps * gi;
+      acc[r] = loc[r];
+    }
+    // loc + L z, MultivariateNormal(loc, scale_tril=L).sample(): k_ram's column sweep (clamped index, the term's input
+    // selected to zero: DESIGN.md 4.4) with the running sum of a row started at its loc, so that L = sqrt(step) I makes the
+    // one multiply-add per row that k_mala makes
+    for (int j = 0; j < P; ++j) {
+      const T zj = w[j];
+      const T* col = S + ram_col(j, P) - j;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int i = lane + r * WAVE;
+        const bool on = i >= j && i < P;
+        const T s = col[on ? i : j];
+        acc[r] += (on ? s : T(0)) * zj;
+      }
+    }
+    T d[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      const bool on = i < P;
+      *(on ? prop + i : w + (P - 1)) = acc[r];  // a lane without a row stores into z's slot, which is spent
+      d[r] = on ? acc[r] - loc[r] : T(0);
+    }
+    const T qf = tril_solve_sq<T>(S, P, d[0], d[1], lane);  // the reference solves for it too (log_prob(proposed), :60)
+    __syncthreads();
+    // inlined here whatever the other kernels of this file do with it: out of line (TinyDyn in f64), the call makes this
+    // kernel save its live registers to scratch around it
+    T tv;
+    [[clang::always_inline]] tv = eval_target<T, true, TINY>(m, l, prop, gp, ht, tc, nullptr, nullptr);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = lane + r * WAVE;
+      const bool on = i < P;
+      const int ii = on ? i : P - 1;
+      const T loc2 = prop[ii] + T(0.5) * eps * gp[ii];
+      d[r] = on ? l.th[ii] - loc2 : T(0);
+    }
+    const T qb = tril_solve_sq<T>(S, P, d[0], d[1], lane);
+    const T log_rate = ((tv - t_state) + T(0.5) * qf) - T(0.5) * qb;  // mala.py:58-64, the constants cancelled
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    const T u = u_in ? u_in[c] : ey_rng_uniform<T>(ru);
+    const bool acc_ = Num<T>::log(u) < log_rate;  // mala.py:66
+    if (acc_) {
+      t_state = tv;
+      for (int i = lane; i < P; i += WAVE) {
+        theta[c * P + i] = prop[i];
+        grad[c * P + i] = gp[i];
+      }
+    }
+    if (run.samples) {
+      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
+      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? prop[i] : l.th[i];
+    }
+    if (lane == 0) {
+      if (acc_) target[c] = tv;
+      accepted[c] = acc_ ? 1 : 0;
+      if (log_rate_o) log_rate_o[c] = log_rate;
+      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
+      if (run.accept_count && acc_) run.accept_count[c] += 1;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, class TINY>
+static int launch_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                            const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                            const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                            void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
+  const size_t bytes = ey_generic_mala_tril_lds(pl);
+  int rc;
+  if ((rc = prep(k_mala_tril<T, TINY>, bytes))) return rc;
+  hipLaunchKernelGGL((k_mala_tril<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
+                     (T*)grad, (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (T)step,
+                     (const T*)step_vec, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
+                     run ? *run : one, C);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+
+size_t ey_generic_mala_tril_lds(const ey_plan* pl) {
+  const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
+  return lds_bytes(pl->m, 4, esz) + mh_tril_extra_bytes(pl->m.P, esz);
+}
+
+int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                         const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                         const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
+                         void* log_rate, hipStream_t s, const EyRun* run) {
+  if (pl->m.P > RAM_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "MALA with a factor: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
+                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
+  if (ey_generic_mala_tril_lds(pl) > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "MALA with a factor: the factor and the model's evaluation image (" +
+                                    std::to_string(ey_generic_mala_tril_lds(pl)) +
+                                    " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_TINY_DISPATCH(launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C,
+                          seed, iter, chain_offset, accepted, log_rate, s, run);
+}
+
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
 // Gibbs.draw (eeyore/samplers/gibbs.py:67-102): per draw, S accept/reject sub-steps, each a Normal random-walk proposal
 // for one block of parameters and one evaluation of the whole log-target.  The kernel knows nothing of nodes: it walks a

@@ -481,6 +481,40 @@ class Plan:
         self._stepped(n_iters)
         return out
 
+    def mala_tril_step(self, theta, target, grad, step, tril, index=None, z=None, u=None, step_vec=None, temp=None, seed=0,
+                       it=0, chain_offset=0, flags=0, out=None):
+        """One MALA.draw of every chain with the proposal theta + step/2 grad + L z (ey_mala_tril_step): ``tril`` and
+        ``index`` as in ``mh_tril_step``, the rest as in ``mala_step``.  Only the lower triangle is read."""
+        C = self._theta(theta)
+        G, index = self._tril(tril, index, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
+        temp, step_vec, u = self._opt(temp, C), self._opt(step_vec, C), self._opt(u, C)
+        L.check(L.lib().ey_mala_tril_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G,
+                                          L.ptr(index), L.ptr(z), L.ptr(u), float(step), L.ptr(step_vec), L.ptr(temp), C,
+                                          int(seed), int(it), int(chain_offset), int(flags), L.ptr(out["accepted"]),
+                                          L.ptr(out["log_rate"]), _stream(self.device)), "ey_mala_tril_step")
+        self._stepped()
+        return out
+
+    def mala_tril_run(self, theta, target, grad, step, tril, n_iters, index=None, step_vec=None, temp=None, seed=0, it=0,
+                      chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
+        """``n_iters`` iterations of ``mala_tril_step`` in one launch (ey_mala_tril_run); records as in ``hmc_run``."""
+        C = self._theta(theta)
+        G, index = self._tril(tril, index, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8))
+        temp, step_vec = self._opt(temp, C), self._opt(step_vec, C)
+        n_iters = int(n_iters)
+        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
+        L.check(L.lib().ey_mala_tril_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G,
+                                         L.ptr(index), float(step), L.ptr(step_vec), L.ptr(temp), C, int(seed), int(it),
+                                         int(chain_offset), int(flags), n_iters, L.ptr(samples), L.ptr(targets),
+                                         L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
+                                         _stream(self.device)), "ey_mala_tril_run")
+        self._stepped(n_iters)
+        return out
+
     def _chol(self, chol, C):
         if (chol.device != self.device or chol.dtype != self.dtype or not chol.is_contiguous()
                 or tuple(chol.shape) != (C, self.P, self.P)):

@@ -16,6 +16,9 @@ import torch
 
 from eeyore_amd.chains import ChainBuffer, ChainList
 from eeyore_amd.datasets import DataCounter, batches
+from eeyore_amd.kernels import check_scale_tril
+
+TRIL_MAX_P = 128  # ey_mh_tril_step / ey_mala_tril_step keep the proposal factor in LDS
 
 
 class Sampler:
@@ -237,6 +240,22 @@ class SingleChainSerialSampler(SerialSampler):
         if torch.is_tensor(self.step) and self.step.dim() == 1:
             return 0.0, self.step
         return float(self.step), None
+
+    def _set_tril(self, scale_tril, index=None):
+        """Take the proposal factor(s) of a MultivariateNormalKernel to the device, checked: [P, P], [C, P, P], or
+        [G, P, P] with ``index`` (int32 [C]) naming the factor of every chain."""
+        P = self.model.num_params()
+        if P > TRIL_MAX_P:
+            raise ValueError(f"{type(self).__name__}: a MultivariateNormalKernel proposal is limited to {TRIL_MAX_P} "
+                             f"parameters (the model has {P}): the factor lives in LDS")
+        check_scale_tril(scale_tril, P)
+        if index is None and scale_tril.dim() == 3 and scale_tril.shape[0] != self.num_chains:
+            raise ValueError(f"scale_tril holds {scale_tril.shape[0]} factors for {self.num_chains} chains: give one "
+                             f"[{P}, {P}] factor or one per chain")
+        self._tril = scale_tril.detach().to(device=self.model.device, dtype=self.model.dtype).contiguous()
+        self._tril_index = None
+        if index is not None:
+            self._tril_index = torch.as_tensor(index).to(device=self.model.device, dtype=torch.int32).contiguous()
 
     def _state_tensor(self, theta):
         th = theta.detach().to(device=self.model.device, dtype=self.model.dtype)

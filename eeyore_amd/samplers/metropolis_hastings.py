@@ -1,9 +1,7 @@
 import torch
 
 from .base import SingleChainSerialSampler, default_counter
-from eeyore_amd.kernels import MultivariateNormalKernel, NormalKernel, check_scale_tril
-
-MH_TRIL_MAX_P = 128  # ey_mh_tril_step keeps the proposal factor in LDS
+from eeyore_amd.kernels import MultivariateNormalKernel, NormalKernel
 
 
 class MetropolisHastings(SingleChainSerialSampler):
@@ -40,22 +38,6 @@ class MetropolisHastings(SingleChainSerialSampler):
     def default_kernel(self, state):
         unit = torch.ones(self.model.num_params(), dtype=self.model.dtype, device=self.model.device)
         return NormalKernel(state['sample'], unit)
-
-    def _set_tril(self, scale_tril, index=None):
-        """Take the proposal factor(s) of a MultivariateNormalKernel to the device, checked: [P, P], [C, P, P], or
-        [G, P, P] with ``index`` (int32 [C]) naming the factor of every chain."""
-        P = self.model.num_params()
-        if P > MH_TRIL_MAX_P:
-            raise ValueError(f"MetropolisHastings: a MultivariateNormalKernel proposal is limited to {MH_TRIL_MAX_P} "
-                             f"parameters (the model has {P}): the factor lives in LDS")
-        check_scale_tril(scale_tril, P)
-        if index is None and scale_tril.dim() == 3 and scale_tril.shape[0] != self.num_chains:
-            raise ValueError(f"scale_tril holds {scale_tril.shape[0]} factors for {self.num_chains} chains: give one "
-                             f"[{P}, {P}] factor or one per chain")
-        self._tril = scale_tril.detach().to(device=self.model.device, dtype=self.model.dtype).contiguous()
-        self._tril_index = None
-        if index is not None:
-            self._tril_index = torch.as_tensor(index).to(device=self.model.device, dtype=torch.int32).contiguous()
 
     def _evaluate_target(self, plan):
         lik, prior = plan.log_target(self._theta, temp=self._temp())

@@ -37,9 +37,10 @@ class PowerPosteriorSampler(SerialSampler):
 
     ``samplers`` is the reference's list ``[[name, kwargs], ...]``, one entry per temperature; ``name`` is 'MALA' or
     'MetropolisHastings' as in the reference (:71-82), or 'HMC' (an extension the reference does not offer).  All
-    With 'MetropolisHastings' the kwargs of the temperatures may each hold a ``MultivariateNormalKernel`` with a ``[P, P]``
-    ``scale_tril``: every temperature then proposes with its own factor (the identity where none is given), which stays with
-    the temperature when a between-chain move exchanges states.  ``NormalKernel``s are still taken from temperature 0.  All
+    With 'MetropolisHastings' or 'MALA' the kwargs of the temperatures may each hold a ``MultivariateNormalKernel`` with a
+    ``[P, P]`` ``scale_tril``: every temperature then proposes with its own factor (the identity where none is given), which stays with
+    the temperature when a between-chain move exchanges states.  ``NormalKernel``s are still taken from temperature 0
+    ('MetropolisHastings'; 'MALA' has its default proposal or the factors, nothing else).  All
     temperatures are advanced by ONE fused step: the K x R chains (K temperatures, R independent replicas of the whole
     ladder; ``theta0`` of shape [P] gives R = 1, [R, P] gives R ladders) form one chain batch whose per-chain
     temperature vector goes to the HIP kernel (temperature multiplies log-likelihood and log-prior,
@@ -99,27 +100,36 @@ class PowerPosteriorSampler(SerialSampler):
                 return vals[0]
             return torch.tensor(vals, dtype=self.dtype, device=self.device).repeat_interleave(R)
 
+        def temperature_trils():
+            """One factor per temperature from the temperatures' MultivariateNormalKernels, [K, P, P] on the device (state
+            row k * R + r proposes with factor k), or None if no temperature holds one."""
+            kernels = [k.get('kernel') for k in kw]
+            mvn = [isinstance(k, MultivariateNormalKernel) for k in kernels]
+            if not any(mvn):
+                return None
+            P = model.num_params()
+            if any(k is not None and not m for k, m in zip(kernels, mvn)):
+                raise ValueError("the temperatures' kernels must be all NormalKernels or all MultivariateNormalKernels "
+                                 "(a temperature without a kernel proposes with the identity factor)")
+            if any(m and tuple(k.scale_tril.shape) != (P, P) for k, m in zip(kernels, mvn)):
+                raise ValueError(f"a temperature's MultivariateNormalKernel must hold one [{P}, {P}] scale_tril")
+            eye = torch.eye(P, dtype=self.dtype, device=self.device)
+            return torch.stack([k.scale_tril.detach().to(device=self.device, dtype=self.dtype) if m else eye
+                                for k, m in zip(kernels, mvn)])
+
         if name == 'MALA':
             self.sampler = MALA(model, step=per_chain('step', 0.1), **common)
+            trils = temperature_trils()
+            if trils is not None:
+                self.sampler._set_tril(trils, index=torch.arange(K, dtype=torch.int32).repeat_interleave(R))
         elif name == 'HMC':
             ns = {int(k.get('num_steps', 10)) for k in kw}
             if len(ns) != 1:
                 raise ValueError("num_steps must be the same at every temperature")
             self.sampler = HMC(model, step=per_chain('step', 0.1), num_steps=ns.pop(), **common)
         elif name == 'MetropolisHastings':
-            kernels = [k.get('kernel') for k in kw]
-            mvn = [isinstance(k, MultivariateNormalKernel) for k in kernels]
-            if any(mvn):
-                # one factor per temperature: K factors on the device, state row k * R + r proposes with factor k
-                P = model.num_params()
-                if any(k is not None and not m for k, m in zip(kernels, mvn)):
-                    raise ValueError("the temperatures' kernels must be all NormalKernels or all MultivariateNormalKernels "
-                                     "(a temperature without a kernel proposes with the identity factor)")
-                if any(m and tuple(k.scale_tril.shape) != (P, P) for k, m in zip(kernels, mvn)):
-                    raise ValueError(f"a temperature's MultivariateNormalKernel must hold one [{P}, {P}] scale_tril")
-                eye = torch.eye(P, dtype=self.dtype, device=self.device)
-                trils = torch.stack([k.scale_tril.detach().to(device=self.device, dtype=self.dtype) if m else eye
-                                     for k, m in zip(kernels, mvn)])
+            trils = temperature_trils()
+            if trils is not None:
                 self.sampler = MetropolisHastings(model, **common)
                 self.sampler._set_tril(trils, index=torch.arange(K, dtype=torch.int32).repeat_interleave(R))
                 self.sampler.kernel = MultivariateNormalKernel(self.sampler.current['sample'], trils[0])

@@ -100,7 +100,7 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
  * is not exactly symmetric or has a diagonal entry that is not > 0; EY_ERR_UNSUPPORTED: P > 128, M > 16.
  * The plan is born with data and prior "set", ey_plan_kernel says "dist" and ey_plan_num_params P.  It serves
  * ey_log_target (log_lik = the tempered log-density, log_prior = 0), ey_log_target_grad, ey_hmc_*, ey_mala_*, ey_mh_*,
- * ey_mh_tril_*, ey_ram_*, ey_am_* and ey_plan_attach_moments with their usual array semantics; ey_plan_set_data / _set_prior return
+ * ey_mh_tril_*, ey_mala_tril_*, ey_ram_*, ey_am_* and ey_plan_attach_moments with their usual array semantics; ey_plan_set_data / _set_prior return
  * EY_ERR_INVALID, ey_log_lik_rows, ey_gibbs_* and ey_plan_attach_da EY_ERR_UNSUPPORTED; EY_FORCE_GENERIC, the options and
  * the variant switches are accepted and change nothing. */
 int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, const double* mean, const double* prec,
@@ -229,6 +229,29 @@ int ey_mh_tril_run(ey_plan* plan, void* theta, void* target, const void* tril, i
                    const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                    int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
                    void* stream);
+
+/* One MALA.draw (eeyore/samplers/mala.py:46-82) whose kernel is a MultivariateNormalKernel(loc, scale_tril): with
+ * loc = theta + step/2 grad (:35-36) and a FIXED lower-triangular factor L, prop = loc + L z, loc' = prop + step/2 grad(prop),
+ * log_rate = target(prop) - target(theta) + |L^-1 (prop - loc)|^2 / 2 - |L^-1 (theta - loc')|^2 / 2 (the proposal is not
+ * symmetric; each term one forward substitution), accept iff log(u) < log_rate.  step enters the mean only: the proposal
+ * covariance is L L^T as given.  theta, target, grad, z, u, step, step_vec and temp are ey_mala_step's (z = NULL => Philox,
+ * its streams); tril, G and tril_index are ey_mh_tril_step's: tril [G,P,P] row-major device array of the plan's dtype, read
+ * only; only the lower triangle (j <= i) of a factor is read, the strict upper triangle may hold anything; G == 1 one factor,
+ * tril_index == NULL chain c's own (G == C), otherwise factor tril_index[c] (device int32 [C]) clamped into [0, G).
+ * EY_ERR_INVALID: a null theta / target / grad / tril / accepted, step <= 0 without step_vec, n_iters < 1, G < 1,
+ * tril_index == NULL with G neither 1 nor C.  Served by one kernel for every model (whatever ey_plan_kernel reports),
+ * mixture plans included, with P <= 128 whose factor fits beside its evaluation image in LDS; EY_ERR_UNSUPPORTED otherwise,
+ * before any launch and with nothing written.  flags is accepted and ignored.  log_rate [C] output may be NULL. */
+int ey_mala_tril_step(ey_plan* plan, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                      const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                      const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                      void* accepted, void* log_rate, void* stream);
+/* n_iters iterations in one launch (the factor is staged once), records as ey_mala_run; ey_mala_tril_run is bit-identical
+ * to n_iters calls of ey_mala_tril_step with z = u = NULL. */
+int ey_mala_tril_run(ey_plan* plan, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                     const void* tril_index, double step, const void* step_vec, const void* temp, int64_t C, uint64_t seed,
+                     uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets,
+                     void* accepted_rec, void* accept_count, void* accepted, void* stream);
 
 /* The block table of a Gibbs sampler: S sub-steps in visiting order, sub-step s proposing for the parameters
  * blk_idx[blk_off[s] .. blk_off[s+1]) with the Normal scale blk_scale[s].  The table is model-agnostic (blockwise
