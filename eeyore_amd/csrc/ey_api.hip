@@ -86,6 +86,8 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
   m.x = m.y = m.mu = m.inv_var = nullptr;
   m.labels = nullptr;
   m.prior_const = 0.0;
+  m.prior_h = nullptr;
+  m.prior_kind = EY_PRIOR_NORMAL;
   pl->dtype = dtype;
   pl->device = device_id;
   pl->has_data = pl->has_prior = false;
@@ -223,6 +225,7 @@ int ey_plan_destroy(ey_plan* pl) {
   (void)hipFree(pl->d_y);
   (void)hipFree(pl->d_mu);
   (void)hipFree(pl->d_inv_var);
+  (void)hipFree(pl->d_prior_h);
   (void)hipFree(pl->d_labels);
   (void)hipFree(pl->d_xpack);
   (void)hipFree(pl->d_xpack16);
@@ -270,7 +273,12 @@ extern "C" int ey_plan_get_option(const ey_plan* pl, int option, int* value) {
   EY_FAIL(EY_ERR_INVALID, "ey_plan_get_option: unknown option");
 }
 // the fused MFMA kernel serves this plan with the batch it currently holds
+static bool prior_normal(const ey_plan* pl) { return pl->m.prior_kind == EY_PRIOR_NORMAL; }
+static const char* prior_name(const ey_plan* pl) {
+  return pl->m.prior_kind == EY_PRIOR_LAPLACE ? "Laplace" : pl->m.prior_kind == EY_PRIOR_STUDENT_T ? "Student-t" : "Normal";
+}
 static bool use_mfma32(const ey_plan* pl) {
+  if (!prior_normal(pl)) return false;  // the fused families carry Normal-prior code only (ey_plan_set_prior_family)
   if (!pl->mfma32_ok || !(pl->mfma32_data_ok || !pl->has_data)) return false;
   if (pl->mfma32_kind == 2)  // the other 4-32-32 models: the bf16x3 form only, whose LDS image holds 16 row tiles
     return pl->products == EY_PRODUCTS_BF16X3 && !(t_ey_variant & 1) && (!pl->has_data || pl->m.N <= 512);
@@ -292,15 +300,19 @@ static bool prefer_large(const ey_plan* pl) {
 static bool use_large(const ey_plan* pl, int nvec = 3, uint32_t flags = 0) {
   if (is_mix(pl)) return false;  // a mixture plan has one family: the generic kernels on TargetMix
   if (ey_large_needed(pl, nvec)) return true;
+  if (!prior_normal(pl)) return false;  // the generic kernels or nothing (check_ready has refused what does not fit)
   if (flags & EY_FORCE_GENERIC) return false;
   if (EY_VBIT(4) && !pl->mfma32_ok) return true;
   return prefer_large(pl);
 }
 // the fused 16x16x4 kernels serve this plan (any batch size: their data image lives in global memory)
-static bool use_fused16(const ey_plan* pl) { return pl->fused16_ok && !use_mfma32(pl) && !EY_VBIT(4); }
+static bool use_fused16(const ey_plan* pl) {
+  return pl->fused16_ok && prior_normal(pl) && !use_mfma32(pl) && !EY_VBIT(4);
+}
 const char* ey_plan_kernel(const ey_plan* pl) {
   if (!pl) return "generic";
   if (is_mix(pl)) return "dist";
+  if (!prior_normal(pl)) return "generic";
   EyVariantScope vs(pl);
   if (use_mfma32(pl)) return "mfma32";
   if (use_fused16(pl)) return "fused16";
@@ -389,6 +401,80 @@ int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stre
   m.mu = pl->d_mu;
   m.inv_var = pl->d_inv_var;
   m.prior_const = c;
+  m.prior_h = nullptr;
+  m.prior_kind = EY_PRIOR_NORMAL;
+  pl->has_prior = true;
+  return EY_OK;
+}
+
+int ey_plan_prior_family(const ey_plan* pl) { return pl ? pl->m.prior_kind : EY_PRIOR_NORMAL; }
+
+int ey_plan_set_prior_family(ey_plan* pl, int family, const void* loc, const void* scale, const void* df, void* stream) {
+  const char* who = "ey_plan_set_prior_family";
+  if (family == EY_PRIOR_NORMAL) return ey_plan_set_prior(pl, loc, scale, stream);
+  if (!pl || !loc || !scale) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (family != EY_PRIOR_LAPLACE && family != EY_PRIOR_STUDENT_T)
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": family must be EY_PRIOR_NORMAL, EY_PRIOR_LAPLACE or EY_PRIOR_STUDENT_T");
+  const bool st = family == EY_PRIOR_STUDENT_T;
+  if (st && !df) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": EY_PRIOR_STUDENT_T needs df");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a mixture plan has no prior (the density is the target)");
+  hipStream_t s = (hipStream_t)stream;
+  EY_HIP(hipSetDevice(pl->device));
+  EyModel& m = pl->m;
+  const size_t es = esize(pl);
+  const int P = m.P;
+  std::vector<unsigned char> hl(es * P), hs(es * P), hd(st ? es * P : 0);
+  EY_HIP(hipMemcpyAsync(hl.data(), loc, es * P, hipMemcpyDeviceToHost, s));
+  EY_HIP(hipMemcpyAsync(hs.data(), scale, es * P, hipMemcpyDeviceToHost, s));
+  if (st) EY_HIP(hipMemcpyAsync(hd.data(), df, es * P, hipMemcpyDeviceToHost, s));
+  EY_HIP(hipStreamSynchronize(s));
+  auto at = [&](const std::vector<unsigned char>& v, int i) {
+    return es == 4 ? (double)((const float*)v.data())[i] : ((const double*)v.data())[i];
+  };
+  // The theta-independent part of the log-density is summed once here and the per-parameter tables are worked out in
+  // double, then rounded once to the plan's dtype (as ey_plan_set_prior builds 1/sigma^2):
+  //   Laplace.log_prob  = -log(2 b) - |v - loc| / b                                              table 1/b
+  //   StudentT.log_prob = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2 - log(s) - (nu+1)/2 log1p(((v-loc)/s)^2 / nu)
+  //                                                                                 tables 1/(nu s^2), (nu+1)/2
+  // Everything is validated before the plan is touched: a refused call leaves the prior it had.
+  double c = 0.0;
+  std::vector<double> t1(P), t2(st ? P : 0);
+  for (int i = 0; i < P; ++i) {
+    const double lo = at(hl, i), sc = at(hs, i);
+    if (!std::isfinite(lo)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": loc[" + std::to_string(i) + "] is not finite");
+    if (!std::isfinite(sc) || !(sc > 0.0))
+      EY_FAIL(EY_ERR_INVALID, std::string(who) + ": scale[" + std::to_string(i) + "] must be finite and > 0");
+    if (!st) {
+      c += -log(2.0 * sc);
+      t1[i] = 1.0 / sc;
+    } else {
+      const double nu = at(hd, i);
+      if (!std::isfinite(nu) || !(nu > 0.0))
+        EY_FAIL(EY_ERR_INVALID, std::string(who) + ": df[" + std::to_string(i) + "] must be finite and > 0");
+      c += lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846) - log(sc);
+      t1[i] = 1.0 / (nu * sc * sc);
+      t2[i] = 0.5 * (nu + 1.0);
+    }
+  }
+  EY_HIP(hipDeviceSynchronize());  // launches on any stream may still read the tables of the prior this one replaces
+  if (!pl->d_mu) EY_HIP(hipMalloc(&pl->d_mu, es * P));
+  if (!pl->d_inv_var) EY_HIP(hipMalloc(&pl->d_inv_var, es * P));
+  if (st && !pl->d_prior_h) EY_HIP(hipMalloc(&pl->d_prior_h, es * P));
+  std::vector<float> f32;
+  auto upload = [&](void* dst, const std::vector<double>& src) -> hipError_t {
+    if (es == 8) return hipMemcpy(dst, src.data(), es * P, hipMemcpyHostToDevice);
+    f32.assign(src.begin(), src.end());
+    return hipMemcpy(dst, f32.data(), es * P, hipMemcpyHostToDevice);
+  };
+  EY_HIP(hipMemcpy(pl->d_mu, hl.data(), es * P, hipMemcpyHostToDevice));
+  EY_HIP(upload(pl->d_inv_var, t1));
+  if (st) EY_HIP(upload(pl->d_prior_h, t2));
+  pl->prior_uniform = false;  // read by the fused families only, which do not serve this plan
+  m.mu = pl->d_mu;
+  m.inv_var = pl->d_inv_var;
+  m.prior_h = st ? pl->d_prior_h : nullptr;
+  m.prior_const = c;
+  m.prior_kind = family;
   pl->has_prior = true;
   return EY_OK;
 }
@@ -436,10 +522,19 @@ static int da_check(const ey_plan* pl, int64_t C, bool fused, const char* who) {
   return EY_OK;
 }
 
-static int check_ready(const ey_plan* pl, int64_t C, const char* who) {
+// A prior family other than Normal lives in the generic kernels alone: a model whose LDS image they cannot hold (nvec state
+// vectors, as use_large counts them) has no kernel.
+static int prior_fits(const ey_plan* pl, int nvec, const char* who) {
+  if (prior_normal(pl) || is_mix(pl) || !ey_large_needed(pl, nvec)) return EY_OK;
+  EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": a " + prior_name(pl) + " prior is served only for models the generic "
+                              "kernels can hold in the 160 KiB LDS of a CU; this model needs the layerwise kernels, "
+                              "which have a Normal prior only");
+}
+static int check_ready(const ey_plan* pl, int64_t C, const char* who, int nvec = 2) {
   if (!pl) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null plan");
   if (!pl->has_data) EY_FAIL(EY_ERR_STATE, std::string(who) + ": ey_plan_set_data has not been called");
   if (!pl->has_prior) EY_FAIL(EY_ERR_STATE, std::string(who) + ": ey_plan_set_prior has not been called");
+  if (int rcp = prior_fits(pl, nvec, who)) return rcp;
   if (C < 0 || C > 0x7fffffffLL) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": chain count out of range");
   return C == 0 ? 1 : EY_OK;  // 1 = nothing to do (an empty chain batch has null buffers)
 }
@@ -452,10 +547,11 @@ int ey_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, v
   if (!log_lik && !pl->has_data && pl->has_prior) {
     if (!theta) EY_FAIL(EY_ERR_INVALID, "ey_log_target: null theta");
     if (C <= 0) return EY_OK;
+    if (int rcp = prior_fits(pl, 3, "ey_log_target")) return rcp;
     EY_HIP(hipSetDevice(pl->device));
     return ey_generic_log_target(pl, theta, temp, C, nullptr, log_prior, nullptr, nullptr, (hipStream_t)stream);
   }
-  int rc = check_ready(pl, C, "ey_log_target");
+  int rc = check_ready(pl, C, "ey_log_target", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   if (!theta) EY_FAIL(EY_ERR_INVALID, "ey_log_target: null theta");
   if (C == 0) return EY_OK;
@@ -467,7 +563,7 @@ int ey_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, v
 
 int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, void* stream) {
   if (pl && is_mix(pl)) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: a mixture plan has no data rows");
-  int rc = check_ready(pl, C, "ey_log_lik_rows");
+  int rc = check_ready(pl, C, "ey_log_lik_rows", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !rows) EY_FAIL(EY_ERR_INVALID, "ey_log_lik_rows: null argument");
@@ -479,7 +575,7 @@ int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C,
 
 int ey_log_target_grad(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* target, void* grad,
                        void* stream) {
-  int rc = check_ready(pl, C, "ey_log_target_grad");
+  int rc = check_ready(pl, C, "ey_log_target_grad", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !target || !grad) EY_FAIL(EY_ERR_INVALID, "ey_log_target_grad: null argument");
@@ -495,7 +591,7 @@ int ey_hmc_step(ey_plan* pl, void* theta, void* target, void* grad, const void* 
                 const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                 uint64_t chain_offset, uint32_t flags, void* accepted, void* accept_rate, void* H_cur, void* H_prop,
                 void* stream) {
-  int rc = check_ready(pl, C, "ey_hmc_step");
+  int rc = check_ready(pl, C, "ey_hmc_step", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, "ey_hmc_step: null argument");
@@ -536,7 +632,7 @@ int ey_hmc_run(ey_plan* pl, void* theta, void* target, void* grad, double step, 
                const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
                void* stream) {
-  int rc = check_ready(pl, C, "ey_hmc_run");
+  int rc = check_ready(pl, C, "ey_hmc_run", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, "ey_hmc_run: null argument");
@@ -602,7 +698,7 @@ int ey_hmc_run(ey_plan* pl, void* theta, void* target, void* grad, double step, 
 
 int ey_hmc_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                     int64_t C, void* target, void* grad, void* stream) {
-  int rc = check_ready(pl, C, "ey_hmc_leapfrog");
+  int rc = check_ready(pl, C, "ey_hmc_leapfrog", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !p || !target || !grad) EY_FAIL(EY_ERR_INVALID, "ey_hmc_leapfrog: null argument");
@@ -654,7 +750,7 @@ static int mala_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
                      const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                      uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate, void* stream,
                      const EyRun* run, const char* who) {
-  int rc = check_ready(pl, C, who);
+  int rc = check_ready(pl, C, who, 4);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
   if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");

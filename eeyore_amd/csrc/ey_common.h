@@ -50,8 +50,10 @@ struct EyModel {
   const void* y;        // [N, dK]; EY_KIND_MIX: prec [M, P, P], row-major, symmetric
   const int* labels;    // [N] argmax(y,1) (CE)
   const void* mu;       // [P]; EY_KIND_MIX: c [M]
-  const void* inv_var;  // [P] 1/sigma^2
-  double prior_const;   // sum_i (-log sigma_i - 0.5 log 2pi)
+  const void* inv_var;  // [P] 1/sigma^2; EY_PRIOR_LAPLACE: 1/b; EY_PRIOR_STUDENT_T: 1/(nu s^2)
+  double prior_const;   // sum_i (-log sigma_i - 0.5 log 2pi); the other families: the table of ey_plan_set_prior_family
+  const void* prior_h;  // [P] EY_PRIOR_STUDENT_T: (nu + 1)/2; null otherwise
+  int prior_kind;       // EY_PRIOR_NORMAL / _LAPLACE / _STUDENT_T: which loop the tail of eval_target runs (ey_generic.hip)
 };
 
 struct ey_plan {
@@ -60,6 +62,7 @@ struct ey_plan {
   int device;
   bool has_data, has_prior;
   void *d_x, *d_y, *d_mu, *d_inv_var;
+  void* d_prior_h = nullptr;  // the third prior table (EyModel::prior_h), allocated on first use
   bool prior_uniform = false;  // every parameter has the same (mu, sigma)
   double prior_mu0 = 0.0, prior_iv0 = 0.0;
   // running moments attached with ey_plan_attach_moments (caller-owned device memory)

@@ -30,6 +30,8 @@ struct Num<float> {
   static __device__ float log(float v) { return logf(v); }
   static __device__ float tanh(float v) { return tanhf(v); }
   static __device__ float sqrt(float v) { return sqrtf(v); }
+  static __device__ float log1p(float v) { return log1pf(v); }
+  static __device__ float abs(float v) { return fabsf(v); }
 };
 template <>
 struct Num<double> {
@@ -37,6 +39,8 @@ struct Num<double> {
   static __device__ double log(double v) { return ::log(v); }
   static __device__ double tanh(double v) { return ::tanh(v); }
   static __device__ double sqrt(double v) { return ::sqrt(v); }
+  static __device__ double log1p(double v) { return ::log1p(v); }
+  static __device__ double abs(double v) { return ::fabs(v); }
 };
 
 template <typename T>
@@ -678,10 +682,38 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
   }  // !TINY
   __syncthreads();
   lik = wave_sum(lik);
-  // ---- prior (bayesian_model.py:46-50), elementwise Normal(mu, sigma)
+  // ---- prior (bayesian_model.py:46-50), elementwise Normal(mu, sigma), or Laplace / Student-t (ey_plan_set_prior_family)
   const T* mu = static_cast<const T*>(m.mu);
   const T* iv = static_cast<const T*>(m.inv_var);
   T q = T(0);
+  // m.prior_kind is a kernel argument: the branch is scalar, one family's loop runs and every lane of the wave runs it
+  if (m.prior_kind == EY_PRIOR_LAPLACE) {
+    // -|d| / b per parameter (iv holds 1/b); the derivative of |d| is sign(d) with sign(0) = 0, what autograd gives at the kink
+    EY_LANE_PASS(m.P, i, on) {
+      const T d = th[i] - mu[i];
+      const T dz = on ? d : T(0);
+      q += Num<T>::abs(dz) * iv[i];
+      if (GRAD) {
+        const T sg = d > T(0) ? T(1) : (d < T(0) ? T(-1) : T(0));
+        T g = gr[i] - sg * iv[i];
+        if (has_temp) g *= temp;
+        gr[i] = g;
+      }
+    }
+  } else if (m.prior_kind == EY_PRIOR_STUDENT_T) {
+    // -h log1p(d^2 w) per parameter (iv holds w = 1/(nu s^2), hh holds h = (nu+1)/2); Cauchy is nu = 1
+    const T* hh = static_cast<const T*>(m.prior_h);
+    EY_LANE_PASS(m.P, i, on) {
+      const T d = th[i] - mu[i];
+      const T dz = on ? d : T(0);
+      q += hh[i] * Num<T>::log1p(dz * dz * iv[i]);
+      if (GRAD) {
+        T g = gr[i] - T(2) * hh[i] * d * iv[i] / (T(1) + d * d * iv[i]);
+        if (has_temp) g *= temp;
+        gr[i] = g;
+      }
+    }
+  } else
   // (EY_LANE_PASS: the same trip count in every lane -- a sum carried across a loop whose last round runs under a partial
   // EXEC mask is what the fast-allocator build of this unit got wrong)
   EY_LANE_PASS(m.P, i, on) {
@@ -696,6 +728,7 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
   }
   q = wave_sum(q);
   T prior = T(m.prior_const) - T(0.5) * q;
+  if (m.prior_kind != EY_PRIOR_NORMAL) prior = T(m.prior_const) - q;
   if (has_temp) { lik *= temp; prior *= temp; }
   if (lik_out) *lik_out = lik;
   if (prior_out) *prior_out = prior;

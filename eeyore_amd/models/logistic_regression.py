@@ -9,6 +9,7 @@ from torch.distributions import Normal
 from eeyore_amd.plan import Plan
 
 from .base import BayesianModel
+from .priors import EY_PRIOR_NORMAL, prior_tables
 from .mlp import activation_code
 
 
@@ -63,9 +64,11 @@ class LogisticRegression(BayesianModel):
                         [activation_code(self.hp.activation)], code, self.dtype, self.device)
             object.__setattr__(self, "_hip_plan", plan)
         if not self._prior_uploaded:
-            if not isinstance(self._prior, Normal):
-                raise ValueError("only an elementwise torch.distributions.Normal prior has a HIP kernel")
-            plan.set_prior(self._prior.loc, self._prior.scale)
+            family, loc, scale, df = prior_tables(self._prior, plan.P)
+            if family == EY_PRIOR_NORMAL:
+                plan.set_prior(loc, scale)
+            else:
+                plan.set_prior_family(family, loc, scale, df)
             object.__setattr__(self, "_prior_uploaded", True)
         if x is not None:
             plan.set_data(x, y)

@@ -228,6 +228,24 @@ class Plan:
         L.check(L.lib().ey_plan_set_prior(self.handle, L.ptr(mu), L.ptr(sigma), _stream(self.device)),
                 "ey_plan_set_prior")
 
+    def set_prior_family(self, family, loc, scale, df=None):
+        """An elementwise prior of another family (ey_plan_set_prior_family): ``family`` is ``EY_PRIOR_NORMAL``,
+        ``EY_PRIOR_LAPLACE`` or ``EY_PRIOR_STUDENT_T`` of ``eeyore_amd._lib`` (a Cauchy prior is Student-t with ``df`` = 1);
+        ``loc``, ``scale`` and, for Student-t, ``df`` broadcast to [P].  The library validates the tables on the host
+        (``ValueError``) before it stores anything.  A plan whose family is not Normal runs on the generic kernels only:
+        ``kernel`` says 'generic', and a model they cannot hold in LDS raises on every operation."""
+        loc = self._prep(torch.broadcast_to(torch.as_tensor(loc), (self.P,)), (self.P,))
+        scale = self._prep(torch.broadcast_to(torch.as_tensor(scale), (self.P,)), (self.P,))
+        if df is not None:
+            df = self._prep(torch.broadcast_to(torch.as_tensor(df), (self.P,)), (self.P,))
+        L.check(L.lib().ey_plan_set_prior_family(self.handle, int(family), L.ptr(loc), L.ptr(scale), L.ptr(df),
+                                                 _stream(self.device)), "ey_plan_set_prior_family")
+
+    @property
+    def prior_family(self):
+        """``EY_PRIOR_NORMAL`` / ``_LAPLACE`` / ``_STUDENT_T``: the family of the prior the plan holds."""
+        return L.lib().ey_plan_prior_family(self.handle)
+
     # ------------------------------------------------------------------ helpers
     def _theta(self, theta):
         if theta.device != self.device or theta.dtype != self.dtype or not theta.is_contiguous():

@@ -122,6 +122,23 @@ int ey_plan_get_option(const ey_plan* plan, int option, int* value);
 int ey_plan_set_data(ey_plan* plan, const void* x, const void* y, int64_t N, void* stream);
 /* model.prior = Normal(mu, sigma) elementwise (eeyore/models/mlp.py:31-35).  mu, sigma [P].  Copied. */
 int ey_plan_set_prior(ey_plan* plan, const void* mu, const void* sigma, void* stream);
+/* model.prior = Laplace(loc, scale) / StudentT(df, loc, scale) / Cauchy(loc, scale) elementwise: any prior the reference
+ * sums as prior.log_prob(theta) parameter by parameter (eeyore/models/bayesian_model.py:46-50).
+ *   EY_PRIOR_LAPLACE    log p = sum_i -log(2 b_i) - |theta_i - loc_i| / b_i; the gradient takes sign(0) = 0
+ *   EY_PRIOR_STUDENT_T  log p = sum_i lgamma((nu_i+1)/2) - lgamma(nu_i/2) - log(nu_i pi)/2 - log s_i
+ *                                     - (nu_i+1)/2 log1p((theta_i - loc_i)^2 / (nu_i s_i^2));  Cauchy is nu = 1
+ * loc, scale, df: [P] device arrays of the plan's dtype, copied; df is read for EY_PRIOR_STUDENT_T only and may be NULL
+ * otherwise.  EY_PRIOR_NORMAL here is exactly ey_plan_set_prior(plan, loc, scale, stream), and ey_plan_set_prior sets the
+ * family back to Normal.  Validated on the host before anything is stored -- EY_ERR_INVALID: an unknown family, a loc that is
+ * not finite, a scale or df that is not finite and > 0, a mixture plan.  The tables are built in double and rounded once
+ * to the plan's dtype.
+ * A plan whose family is not Normal is served by the "generic" kernels only, whatever the model (ey_plan_kernel says so):
+ * every operation of a model whose generic LDS image does not fit a CU returns EY_ERR_UNSUPPORTED, and in-kernel dual
+ * averaging (ey_plan_attach_da) is refused as for every generic plan.  Setting a Normal prior again restores the plan's
+ * routing and its results bit for bit. */
+enum ey_prior_family { EY_PRIOR_NORMAL = 0, EY_PRIOR_LAPLACE = 1, EY_PRIOR_STUDENT_T = 2 };
+int ey_plan_set_prior_family(ey_plan* plan, int family, const void* loc, const void* scale, const void* df, void* stream);
+int ey_plan_prior_family(const ey_plan* plan);
 
 /* BayesianModel.log_lik / log_prior / log_target (eeyore/models/bayesian_model.py:30-56) for C chains.
  * temp: per-chain temperature [C] or NULL (model.temperature = None); multiplies BOTH outputs (:33-34,48-49).
