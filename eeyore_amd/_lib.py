@@ -21,6 +21,7 @@ _vp, _i, _i64, _u64, _u32, _d = ct.c_void_p, ct.c_int, ct.c_int64, ct.c_uint64, 
 EY_OPT_F32_PRODUCTS, EY_PRODUCTS_BF16X3, EY_PRODUCTS_EXACT = 1, 0, 1
 EY_OPT_ROW_WAVES, EY_ROW_WAVES_OFF, EY_ROW_WAVES_ON, EY_ROW_WAVES_AUTO = 2, 0, 1, 2
 EY_PRIOR_NORMAL, EY_PRIOR_LAPLACE, EY_PRIOR_STUDENT_T = 0, 1, 2
+EY_LIK_BCE_SUM, EY_LIK_CE_SUM, EY_LIK_GAUSS_SUM, EY_LIK_LAPLACE_SUM, EY_LIK_POISSON_SUM = 0, 1, 2, 3, 4
 
 SYMBOLS = {
     "ey_version": (_i, []),
@@ -34,6 +35,9 @@ SYMBOLS = {
     "ey_plan_set_prior": (_i, [_vp, _vp, _vp, _vp]),
     "ey_plan_set_prior_family": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "ey_plan_prior_family": (_i, [_vp]),
+    "ey_plan_set_lik_scale": (_i, [_vp, _d]),
+    "ey_plan_lik_scale": (_d, [_vp]),
+    "ey_forward": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "ey_log_target": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ey_log_target_grad": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ey_hmc_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp,

@@ -1,1 +1,2 @@
-from .constants import loss_functions, torch_to_np_types, Loss
+from .constants import (Loss, gaussian_loss, laplace_loss, loss_functions, poisson_loss,  # noqa: F401
+                        torch_to_np_types)

@@ -36,6 +36,18 @@ int ey_default_products() {
 }
 
 static size_t esize(const ey_plan* pl) { return pl->dtype == EY_F32 ? 4 : 8; }
+// The constants of EY_LIK_GAUSS_SUM / _LAPLACE_SUM for the scale s, in double, rounded once to the plan's dtype (as the prior
+// tables are): lik_w = 1/s^2 or 1/s, lik_c = the log-normaliser of one output.  The other codes read neither.
+static void set_lik_constants(ey_plan* pl, double s) {
+  EyModel& m = pl->m;
+  double w = 0.0, c = 0.0;
+  if (m.lik == EY_LIK_GAUSS_SUM) { w = 1.0 / (s * s); c = -log(s) - 0.91893853320467274178; }
+  if (m.lik == EY_LIK_LAPLACE_SUM) { w = 1.0 / s; c = -log(2.0 * s); }
+  if (pl->dtype == EY_F32) { w = (double)(float)w; c = (double)(float)c; }
+  m.lik_w = w;
+  m.lik_c = c;
+  pl->lik_scale = s;
+}
 static bool is_mix(const ey_plan* pl) { return pl->m.kind == EY_KIND_MIX; }
 
 extern "C" {
@@ -50,7 +62,7 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
   // single layer (logistic regression, eeyore/models/logistic_regression.py) is accepted as the K=1 case.
   if (n_layers < 1 || n_layers > EY_MAX_LAYERS) EY_FAIL(EY_ERR_INVALID, "ey_plan_create: n_layers must be in 1..8");
   if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, "ey_plan_create: dtype must be EY_F32 or EY_F64");
-  if (likelihood != EY_LIK_BCE_SUM && likelihood != EY_LIK_CE_SUM)
+  if (likelihood < EY_LIK_BCE_SUM || likelihood > EY_LIK_POISSON_SUM)
     EY_FAIL(EY_ERR_INVALID, "ey_plan_create: unknown likelihood");
   for (int l = 0; l <= n_layers; ++l)
     if (dims[l] < 1) EY_FAIL(EY_ERR_INVALID, "ey_plan_create: dims must be positive");
@@ -89,6 +101,7 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
   m.prior_h = nullptr;
   m.prior_kind = EY_PRIOR_NORMAL;
   pl->dtype = dtype;
+  set_lik_constants(pl, 1.0);
   pl->device = device_id;
   pl->has_data = pl->has_prior = false;
   pl->d_x = pl->d_y = pl->d_mu = pl->d_inv_var = nullptr;
@@ -344,7 +357,8 @@ int ey_plan_set_data(ey_plan* pl, const void* x, const void* y, int64_t N, void*
   EY_HIP(hipMemcpyAsync(pl->d_x, x, es * N * d0, hipMemcpyDeviceToDevice, s));
   EY_HIP(hipMemcpyAsync(pl->d_y, y, es * N * dK, hipMemcpyDeviceToDevice, s));
   const dim3 grid((unsigned)((N + 255) / 256));
-  if (es == 4) hipLaunchKernelGGL(k_labels<float>, grid, dim3(256), 0, s, (const float*)pl->d_y, pl->d_labels, N, dK);
+  if (ey_lik_regression(m.lik)) {}  // no kernel of a regression plan reads labels
+  else if (es == 4) hipLaunchKernelGGL(k_labels<float>, grid, dim3(256), 0, s, (const float*)pl->d_y, pl->d_labels, N, dK);
   else hipLaunchKernelGGL(k_labels<double>, grid, dim3(256), 0, s, (const double*)pl->d_y, pl->d_labels, N, dK);
   EY_HIP(hipGetLastError());
   m.N = (int)N;
@@ -408,6 +422,18 @@ int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stre
 }
 
 int ey_plan_prior_family(const ey_plan* pl) { return pl ? pl->m.prior_kind : EY_PRIOR_NORMAL; }
+
+double ey_plan_lik_scale(const ey_plan* pl) { return pl ? pl->lik_scale : 1.0; }
+
+int ey_plan_set_lik_scale(ey_plan* pl, double s) {
+  const char* who = "ey_plan_set_lik_scale";
+  if (!pl) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null plan");
+  if (is_mix(pl) || (pl->m.lik != EY_LIK_GAUSS_SUM && pl->m.lik != EY_LIK_LAPLACE_SUM))
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": only a plan of EY_LIK_GAUSS_SUM or EY_LIK_LAPLACE_SUM has a likelihood scale");
+  if (!std::isfinite(s) || !(s > 0.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the scale must be finite and > 0");
+  set_lik_constants(pl, s);  // kernel arguments of the launches that follow: nothing on the device changes
+  return EY_OK;
+}
 
 int ey_plan_set_prior_family(ey_plan* pl, int family, const void* loc, const void* scale, const void* df, void* stream) {
   const char* who = "ey_plan_set_prior_family";
@@ -571,6 +597,23 @@ int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C,
   EY_HIP(hipSetDevice(pl->device));
   if (use_large(pl)) return ey_large_log_lik_rows(pl, theta, temp, C, rows, (hipStream_t)stream);
   return ey_generic_log_lik_rows(pl, theta, temp, C, rows, (hipStream_t)stream);
+}
+
+int ey_forward(ey_plan* pl, const void* theta, int64_t C, void* out, void* stream) {
+  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_forward: a mixture plan has no network");
+  // (not check_ready: a prior family the layerwise kernels do not serve is no obstacle, their forward products read no prior)
+  if (!pl) EY_FAIL(EY_ERR_INVALID, "ey_forward: null plan");
+  if (!pl->has_data) EY_FAIL(EY_ERR_STATE, "ey_forward: ey_plan_set_data has not been called");
+  if (!pl->has_prior) EY_FAIL(EY_ERR_STATE, "ey_forward: ey_plan_set_prior has not been called");
+  if (C < 0 || C > 0x7fffffffLL) EY_FAIL(EY_ERR_INVALID, "ey_forward: chain count out of range");
+  if (C == 0) return EY_OK;
+  EyVariantScope vs(pl);
+  if (!theta || !out) EY_FAIL(EY_ERR_INVALID, "ey_forward: null argument");
+  EY_HIP(hipSetDevice(pl->device));
+  // whatever family serves the plan's draws: the generic value kernel when its LDS image (two state vectors) holds the
+  // model, the layerwise forward products otherwise; the fused families have no such output
+  if (ey_large_needed(pl, 2)) return ey_large_forward(pl, theta, C, out, (hipStream_t)stream);
+  return ey_generic_forward(pl, theta, C, out, (hipStream_t)stream);
 }
 
 int ey_log_target_grad(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* target, void* grad,

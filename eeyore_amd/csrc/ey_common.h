@@ -54,7 +54,12 @@ struct EyModel {
   double prior_const;   // sum_i (-log sigma_i - 0.5 log 2pi); the other families: the table of ey_plan_set_prior_family
   const void* prior_h;  // [P] EY_PRIOR_STUDENT_T: (nu + 1)/2; null otherwise
   int prior_kind;       // EY_PRIOR_NORMAL / _LAPLACE / _STUDENT_T: which loop the tail of eval_target runs (ey_generic.hip)
+  // EY_LIK_GAUSS_SUM / _LAPLACE_SUM (ey_plan_set_lik_scale): worked out in double, rounded once to the plan's dtype
+  double lik_w;         // 1/s^2 (Gaussian), 1/s (Laplace)
+  double lik_c;         // the log-normaliser of one output: -log(s sqrt(2 pi)) (Gaussian), -log(2 s) (Laplace)
 };
+// the regression codes: served by the generic kernels and the separate layerwise launches only
+static inline bool ey_lik_regression(int lik) { return lik >= EY_LIK_GAUSS_SUM; }
 
 struct ey_plan {
   EyModel m;
@@ -63,6 +68,7 @@ struct ey_plan {
   bool has_data, has_prior;
   void *d_x, *d_y, *d_mu, *d_inv_var;
   void* d_prior_h = nullptr;  // the third prior table (EyModel::prior_h), allocated on first use
+  double lik_scale = 1.0;     // s of EY_LIK_GAUSS_SUM / _LAPLACE_SUM (ey_plan_set_lik_scale)
   bool prior_uniform = false;  // every parameter has the same (mu, sigma)
   double prior_mu0 = 0.0, prior_iv0 = 0.0;
   // running moments attached with ey_plan_attach_moments (caller-owned device memory)
@@ -175,6 +181,7 @@ int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int6
                           void* target, void* grad, hipStream_t s);
 void ey_generic_mix_scratch(EyModel& m);  // hrows / dmax of an EY_KIND_MIX model: the evaluation scratch of mix_target
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
+int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s);  // out [C, N, dK] (ey_forward)
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
                    const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                    uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
@@ -251,6 +258,7 @@ int ey_large_mala_mh(ey_plan* pl, void* theta, void* target, void* grad, const v
 int ey_large_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                       int64_t C, void* target, void* grad, hipStream_t s);
 int ey_large_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
+int ey_large_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s);  // out [C, N, dK] (ey_forward)
 void ey_large_free(ey_plan* pl);
 
 // mfma32 kernels (ey_mfma32.hip)

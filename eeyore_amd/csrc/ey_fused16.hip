@@ -1188,6 +1188,8 @@ __global__ void k_f16_pack(const T* __restrict__ x, const T* __restrict__ y, con
 bool ey_fused16_supports(const ey_plan* pl) {
   const EyModel& m = pl->m;
   if (m.nl != 3 && m.nl != 2) return false;
+  // CE-sum and BCE-sum only: a regression code on MLP(4-32-32-1) with an identity output passes every check below
+  if (m.lik != EY_LIK_CE_SUM && m.lik != EY_LIK_BCE_SUM) return false;
   const int K = m.nl;              // two hidden layers, or one (the middle layer of the kernel is then skipped)
   const int h1 = m.dims[1], h2 = m.dims[K - 1];
   const int H = std::max(h1, h2);  // the tile grid is the next of 16 / 32 / 64; narrower layers are padded

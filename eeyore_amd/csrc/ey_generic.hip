@@ -234,7 +234,7 @@ __device__ __forceinline__ void tiny_act(int code, T (&h)[TINY_DH], int n) {
 // the lanes) and, when GRAD, the gradient of the log-likelihood in gr (LDS, canonical layout).
 template <typename T, bool GRAD, class S>
 __device__ __forceinline__ T tiny_rows(const EyModel& m, const T* th, T* gr, bool has_temp, T temp, T* row_out,
-                                       const RowWaves& rw) {
+                                       const RowWaves& rw, T* fwd_out) {
   const int lane = threadIdx.x & (WAVE - 1);
   const T* x = static_cast<const T*>(m.x);
   const T* y = static_cast<const T*>(m.y);
@@ -291,7 +291,39 @@ __device__ __forceinline__ T tiny_rows(const EyModel& m, const T* th, T* gr, boo
       d[j] = T(0);
     }
     const int act_out = m.act[nl - 1];
+    if (fwd_out && valid) {  // ey_forward: the row's outputs, next to row_out below
+#pragma unroll
+      for (int j = 0; j < TINY_DH; ++j)
+        if (j < dK) fwd_out[(size_t)n * dK + j] = out[j];
+    }
     T row_lik = T(0);
+    // m.lik is a kernel argument: the branches on it are scalar
+    if (m.lik >= EY_LIK_GAUSS_SUM) {
+      // regression (include/eeyore_amd.h: enum ey_lik): r = out - y, lw = 1/s^2 or 1/s, lc the log-normaliser of one output
+      const T lw = T(m.lik_w), lc = T(m.lik_c);
+#pragma unroll
+      for (int j = 0; j < TINY_DH; ++j)
+        if (j < dK) {
+          const T o = out[j];
+          const T yy = valid ? y[(size_t)n * dK + j] : T(0);
+          const T r = o - yy;
+          T term, dd;
+          if (m.lik == EY_LIK_GAUSS_SUM) {
+            term = lc - T(0.5) * r * r * lw;
+            dd = -r * lw;
+          } else if (m.lik == EY_LIK_LAPLACE_SUM) {
+            term = lc - Num<T>::abs(r) * lw;
+            dd = r > T(0) ? -lw : (r < T(0) ? lw : T(0));  // -sign(r) / s with sign(0) = 0
+          } else {  // EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped (an overflowing exp gives a -inf target)
+            const T e = Num<T>::exp(o);
+            term = yy * o - e;
+            dd = yy - e;
+          }
+          lik += valid ? term : T(0);
+          row_lik += term;
+          if (GRAD) d[j] = valid ? dd * dact_fn<T>(act_out, o) : T(0);
+        }
+    } else
     if (m.lik == EY_LIK_BCE_SUM) {
 #pragma unroll
       for (int j = 0; j < TINY_DH; ++j)
@@ -537,7 +569,8 @@ void ey_generic_mix_scratch(EyModel& m) {
 
 template <typename T, bool GRAD, class TINY = TinyOff>
 __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
-                         T* prior_out, T* row_out = nullptr, const RowWaves rw = RowWaves{0, 1, nullptr}) {
+                         T* prior_out, T* row_out = nullptr, const RowWaves rw = RowWaves{0, 1, nullptr},
+                         T* fwd_out = nullptr) {
   if constexpr (std::is_same<TINY, TargetMix>::value)
     return mix_target<T, GRAD>(m, l, th, gr, has_temp, temp, lik_out, prior_out);
   const int lane = threadIdx.x & (WAVE - 1);
@@ -548,7 +581,7 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
   T lik = T(0);
   if constexpr (TINY::on) {
     __syncthreads();  // the position written by the caller is visible
-    lik = tiny_rows<T, GRAD, TINY>(m, th, gr, has_temp, temp, row_out, rw);
+    lik = tiny_rows<T, GRAD, TINY>(m, th, gr, has_temp, temp, row_out, rw, fwd_out);
   } else {
   if (GRAD) {
     for (int i = lane; i < m.P; i += WAVE) gr[i] = T(0);
@@ -597,6 +630,33 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
     T* dcur = l.dl;
     T* dnext = l.dl + m.dmax * TS;
     T row_lik = T(0);  // this row's term of the log-likelihood sum (ey_log_lik_rows)
+    if (fwd_out && valid) {  // ey_forward: the row's outputs, next to row_out below
+      for (int j = 0; j < dK; ++j) fwd_out[(size_t)n * dK + j] = out[j * TS];
+    }
+    if (m.lik >= EY_LIK_GAUSS_SUM) {
+      // regression (include/eeyore_amd.h: enum ey_lik), the arithmetic of tiny_rows: a scalar branch on the kernel argument
+      const T lw = T(m.lik_w), lc = T(m.lik_c);
+      for (int j = 0; j < dK; ++j) {
+        const T o = out[j * TS];
+        const T yy = valid ? y[(size_t)n * dK + j] : T(0);
+        const T r = o - yy;
+        T term, d;
+        if (m.lik == EY_LIK_GAUSS_SUM) {
+          term = lc - T(0.5) * r * r * lw;
+          d = -r * lw;
+        } else if (m.lik == EY_LIK_LAPLACE_SUM) {
+          term = lc - Num<T>::abs(r) * lw;
+          d = r > T(0) ? -lw : (r < T(0) ? lw : T(0));  // -sign(r) / s with sign(0) = 0
+        } else {  // EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped
+          const T e = Num<T>::exp(o);
+          term = yy * o - e;
+          d = yy - e;
+        }
+        if (valid) lik += term;
+        row_lik += term;
+        if (GRAD) dcur[j * TS + lane] = valid ? d * dact_fn<T>(m.act[nl - 1], o) : T(0);
+      }
+    } else
     if (m.lik == EY_LIK_BCE_SUM) {
       for (int j = 0; j < dK; ++j) {
         const T o = out[j * TS];
@@ -759,6 +819,20 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_log_target(EyMode
   if (GRAD && w0) {
     for (int i = lane; i < m.P; i += WAVE) grad_o[c * m.P + i] = l.gr[i];
   }
+}
+
+// ey_forward: the network outputs of every chain, out [C, N, dK].  A kernel of its own, so that k_log_target stays the code it
+// was (its values are held bit-equal to the targets the sampling kernels carry); the value, the prior and the gradient the
+// evaluation also works out are dropped.
+template <typename T, class TINY, bool RW = false>
+__global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_forward(EyModel m, const T* theta, T* out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const RowWaves rw = RW ? row_waves<T>(m, smem, 2) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
+  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 2, sizeof(T)) : 0), 2);
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1);
+  for (int i = lane; i < m.P; i += WAVE) l.th[i] = theta[c * m.P + i];
+  eval_target<T, false, TINY>(m, l, l.th, l.gr, false, T(1), nullptr, nullptr, nullptr, rw, out + c * m.N * m.dims[m.nl]);
 }
 
 template <typename T, class TINY, bool RW = false>
@@ -1116,6 +1190,25 @@ int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int6
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s) {
   if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: this plan has no data rows");
   return EY_TINY_DISPATCH(launch_log_target, pl, theta, temp, C, nullptr, nullptr, nullptr, nullptr, s, rows);
+}
+
+template <typename T, class TINY>
+static int launch_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
+  const int nw = row_waves_for(pl, TINY::on, C);
+  const size_t bytes = lds_total(pl->m, 2, sizeof(T), nw);
+  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
+    constexpr bool RW = decltype(rwtag)::value;
+    int rc;
+    if ((rc = prep(k_forward<T, TINY, RW>, bytes))) return rc;
+    hipLaunchKernelGGL((k_forward<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (const T*)theta, (T*)out);
+    EY_HIP(hipGetLastError());
+    return (int)EY_OK;
+  });
+}
+// ey_forward: out [C, N, dK]
+int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
+  if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_INVALID, "ey_forward: this plan has no network");
+  return EY_TINY_DISPATCH_MLP(launch_forward, pl, theta, C, out, s);
 }
 
 template <typename T, class TINY>

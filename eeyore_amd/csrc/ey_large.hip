@@ -1650,7 +1650,7 @@ template <class T>
 __global__ void __launch_bounds__(256) k_loss(const T* __restrict__ out, T* __restrict__ delta,
                                               const T* __restrict__ y, const int* __restrict__ labels, int N, int dK,
                                               int lik_code, int act_last, T* __restrict__ lik_o,
-                                              T* __restrict__ rows_o, const T* __restrict__ temp) {
+                                              T* __restrict__ rows_o, const T* __restrict__ temp, T lw, T lc) {
   __shared__ T red[4];
   const long c = blockIdx.x;
   const T* o = out + c * (long)N * dK;
@@ -1658,6 +1658,26 @@ __global__ void __launch_bounds__(256) k_loss(const T* __restrict__ out, T* __re
   T lik = T(0.0);
   for (int n = threadIdx.x; n < N; n += blockDim.x) {
     T row = T(0.0);  // this row's term of the sum (ey_log_lik_rows)
+    if (lik_code >= EY_LIK_GAUSS_SUM) {
+      // regression (include/eeyore_amd.h: enum ey_lik): r = out - y, lw = 1/s^2 or 1/s, lc the log-normaliser of one output
+      for (int j = 0; j < dK; ++j) {
+        const T v = o[n * dK + j], yy = y[n * dK + j];
+        const T r = v - yy;
+        T dd;
+        if (lik_code == EY_LIK_GAUSS_SUM) {
+          row += lc - T(0.5) * r * r * lw;
+          dd = -r * lw;
+        } else if (lik_code == EY_LIK_LAPLACE_SUM) {
+          row += lc - (r < T(0.0) ? -r : r) * lw;
+          dd = r > T(0.0) ? -lw : (r < T(0.0) ? lw : T(0.0));  // -sign(r) / s with sign(0) = 0
+        } else {  // EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped
+          const T e = l_exp(v);
+          row += yy * v - e;
+          dd = yy - e;
+        }
+        d[n * dK + j] = dd * l_dact(act_last, v);
+      }
+    } else
     if (lik_code == EY_LIK_BCE_SUM) {
       for (int j = 0; j < dK; ++j) {
         const T p = o[n * dK + j], yy = y[n * dK + j];
@@ -2243,6 +2263,7 @@ __global__ void __launch_bounds__(256, (F * sizeof(T) >= 32) ? 2 : 3) k_tail(Tai
 static int tail_f(int d) { return d <= 16 ? 1 : (d <= 32 ? 2 : 4); }  // vector piece: features that must come whole
 static bool tail_ok(const EyModel& m) {
   const int K = m.nl, d = m.dims[K - 1];
+  if (ey_lik_regression(m.lik)) return false;  // k_tail carries the classification losses only: k_loss serves the others
   if (K < 2 || m.dims[K] > TAIL_DK || d < 1 || d > 128) return false;
   return d % tail_f(d) == 0;
 }
@@ -2433,7 +2454,7 @@ static int eval_chunk(ey_plan* pl, const T* theta, const T* temp, int C, T* lik_
   }
   if (!tail)
     hipLaunchKernelGGL((k_loss<T>), dim3(C), dim3(256), 0, s, (const T*)H[K], D[K], (const T*)m.y, m.labels, N,
-                       m.dims[K], m.lik, m.act[K - 1], lik_tmp, rows_o, rows_o ? temp : nullptr);
+                       m.dims[K], m.lik, m.act[K - 1], lik_tmp, rows_o, rows_o ? temp : nullptr, (T)m.lik_w, (T)m.lik_c);
   const int ltop = tail ? K - 2 : K - 1;
   if (grad) {
     for (int l = ltop; l >= 0; --l) {
@@ -2787,6 +2808,56 @@ static int large_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, 
 }
 int ey_large_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s) {
   return pl->dtype == EY_F32 ? large_log_lik_rows<float>(pl, theta, temp, C, rows, s) : large_log_lik_rows<double>(pl, theta, temp, C, rows, s);
+}
+
+// the network outputs of every chain (ey_forward): the forward products of eval_chunk, the last one written to out [C, N, dK]
+template <class T>
+static int large_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
+  const EyModel& m = pl->m;
+  const int K = m.nl, N = m.N, P = m.P;
+  const int cc = chunk_size(pl, C);
+  const size_t af = act_floats_per_chain(m);
+  int rc = ensure_work(pl, (size_t)cc * af * sizeof(T));
+  if (rc) return rc;
+  T* ws = (T*)pl->d_work;
+  const void* xpre = nullptr;
+  const void* xpreT = nullptr;
+  if constexpr (sizeof(T) == 4) {  // as eval_chunk: the same first-layer product, hence the same outputs as the evaluation's
+    if (t_ey_products == EY_PRODUCTS_BF16X3 && N > 32 && m.dims[1] > 32 && m.dims[0] >= 16 && !EY_VBIT(11))
+      if ((rc = ensure_xpre(pl, s, &xpre, &xpreT))) return rc;
+  }
+  for (int64_t c0 = 0; c0 < C; c0 += cc) {
+    const int n = (int)((C - c0) < cc ? (C - c0) : cc);
+    const T* th = (const T*)theta + c0 * P;
+    std::vector<T*> H(K + 1);
+    size_t off = 0;
+    for (int l = 1; l <= K; ++l) {
+      H[l] = ws + off * n;
+      off += (size_t)N * m.dims[l];
+    }
+    H[K] = (T*)out + c0 * (int64_t)N * m.dims[K];
+    for (int l = 0; l < K; ++l) {
+      BGT<T> g = {};
+      g.A = l == 0 ? (const T*)m.x : H[l];
+      g.B = th + m.woff[l];
+      g.C = H[l + 1];
+      g.M = N; g.N = m.dims[l + 1]; g.K = m.dims[l];
+      g.sAm = m.dims[l]; g.sAk = 1; g.bA = l == 0 ? 0 : (long)N * m.dims[l];
+      g.sBk = 1; g.sBn = m.dims[l]; g.bB = P;
+      g.sCm = m.dims[l + 1]; g.sCn = 1; g.bC = (long)N * m.dims[l + 1];
+      g.bias = m.boff[l] >= 0 ? th + m.boff[l] : nullptr; g.bBias = P;
+      g.act = m.act[l];
+      if constexpr (sizeof(T) == 4) {
+        if (l == 0 && xpre) { g.pre = xpre; g.pre_rows = N; }
+      }
+      if ((rc = bgemm(g, n, s))) return rc;
+    }
+  }
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}
+int ey_large_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
+  return pl->dtype == EY_F32 ? large_forward<float>(pl, theta, C, out, s) : large_forward<double>(pl, theta, C, out, s);
 }
 
 // Test / measurement entry (not part of the sampler surface): C[b] = act(A[b] B[b] + bias[b]) through the same

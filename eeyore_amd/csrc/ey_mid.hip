@@ -1169,6 +1169,7 @@ static bool mid32_plan(const EyModel& m, MidArgs& a) {
 }
 bool ey_mid32_supports(const ey_plan* pl) {
   if (pl->dtype != EY_F32) return false;
+  if (ey_lik_regression(pl->m.lik)) return false;  // the fused kernels carry the classification losses only
   MidArgs a = {};
   return mid32_plan(pl->m, a);
 }
@@ -1230,6 +1231,7 @@ int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, flo
 
 bool ey_mid_supports(const ey_plan* pl) {
   if (pl->dtype != EY_F32) return false;
+  if (ey_lik_regression(pl->m.lik)) return false;  // the fused kernels carry the classification losses only
   MidArgs a = {};
   return mid_plan(pl->m, a);
 }

@@ -169,6 +169,27 @@ class BayesianModel(LogTargetModel):
         est = torch.where(kept > 0, est, torch.full_like(est, float('nan')))
         return est, (~ok).sum(0)
 
+    def predict_batched(self, samples, x):
+        """Posterior predictive mean and spread of the network output at K points: x [K, d_0], ``samples`` the stored
+        samples ([S, P] tensor or a list of [P]).  Returns (mean [K, d_K], sd [K, d_K], dropped [K]): mean and standard
+        deviation (unbiased estimator) over the samples of the output after the last activation -- the regression
+        function under a regression loss, class probabilities or logits under a classification loss.  A sample with a
+        non-finite output at a point is dropped for that point and counted, as ``predictive_posterior_batched`` counts
+        them.  One device pass over S x K (``Plan.forward``); the reduction is in torch."""
+        th = self._stack_samples(samples)
+        y = torch.zeros(x.shape[0], self.hp.dims[-1] if hasattr(self.hp, "dims") else self.hp.output_size,
+                        dtype=self.dtype, device=self.device)  # the batch needs a response; forward never reads it
+        out = self._plan(x, y).forward(th)  # [S, K, dK]
+        ok = torch.isfinite(out).all(dim=2, keepdim=True)  # [S, K, 1]
+        kept = ok.sum(0)  # [K, 1]
+        nan = torch.full_like(out[0], float('nan'))
+        mean = torch.where(ok, out, torch.zeros_like(out)).sum(0) / kept.clamp(min=1)
+        dev = torch.where(ok, out - mean, torch.zeros_like(out))
+        var = (dev * dev).sum(0) / (kept - 1).clamp(min=1)
+        mean = torch.where(kept > 0, mean, nan)
+        sd = torch.where(kept > 1, var.sqrt(), nan)
+        return mean, sd, (~ok).sum(0).reshape(-1)
+
     def predictive_posterior_from_dataset(self, theta, dataset, num_points, shuffle=True, verbose=False, verbose_step=1):
         """(integrals, indices, numbers of dropped samples) as bayesian_model.py:64-67 /
         mcintegrator.py:38-63: points are drawn one at a time from a DataLoader(dataset, batch_size=1, shuffle) exactly

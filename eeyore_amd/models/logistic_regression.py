@@ -24,6 +24,9 @@ class Hyperparameters:
 class LogisticRegression(BayesianModel):
     def __init__(self, loss, temperature=None, prior=None, hparams=Hyperparameters(), savefile=None,
                  dtype=torch.float64, device='cpu'):
+        if getattr(loss, "code", 0) >= 2:
+            raise ValueError(f"{loss!r} is a regression loss: the output of a logistic regression is a probability "
+                             "(use models.mlp.MLP for a continuous or count response)")
         super().__init__(loss, temperature=temperature, dtype=dtype, device=device)
         self.hp = hparams
         self.linear = nn.Linear(self.hp.input_size, self.hp.output_size, bias=self.hp.bias).to(

@@ -132,10 +132,13 @@ class MLP(BayesianModel):
         if plan is None:
             code = getattr(self.loss, "code", None)
             if code is None:
-                raise ValueError("loss must be one of eeyore_amd.constants.loss_functions (the kernels implement "
-                                 "BCE-sum on probabilities and CE-sum on logits)")
+                raise ValueError("loss must be one of eeyore_amd.constants.loss_functions or a loss of its factories "
+                                 "(the kernels implement BCE-sum on probabilities, CE-sum on logits and the Gaussian, "
+                                 "Laplace and Poisson regression likelihoods)")
             acts = [activation_code(a) for a in self.hp.activations]
             plan = Plan(self.hp.dims, self.hp.bias, acts, code, self.dtype, self.device)
+            if getattr(self.loss, "scale", None) is not None:  # the noise scale of a Gaussian or Laplace likelihood
+                plan.set_lik_scale(self.loss.scale)
             object.__setattr__(self, "_hip_plan", plan)
         if not self._prior_uploaded:
             family, loc, scale, df = prior_tables(self._prior, plan.P)

@@ -246,6 +246,16 @@ class Plan:
         """``EY_PRIOR_NORMAL`` / ``_LAPLACE`` / ``_STUDENT_T``: the family of the prior the plan holds."""
         return L.lib().ey_plan_prior_family(self.handle)
 
+    def set_lik_scale(self, scale):
+        """The scale s of a Gaussian or Laplace likelihood (ey_plan_set_lik_scale; the default is 1): one positive number
+        for all outputs.  ``ValueError`` when it is not finite and > 0, or on a plan of a classification or Poisson code."""
+        L.check(L.lib().ey_plan_set_lik_scale(self.handle, float(scale)), "ey_plan_set_lik_scale")
+
+    @property
+    def lik_scale(self):
+        """The scale of the plan's Gaussian or Laplace likelihood (1 for the codes that have none)."""
+        return L.lib().ey_plan_lik_scale(self.handle)
+
     # ------------------------------------------------------------------ helpers
     def _theta(self, theta):
         if theta.device != self.device or theta.dtype != self.dtype or not theta.is_contiguous():
@@ -282,6 +292,15 @@ class Plan:
         L.check(L.lib().ey_log_lik_rows(self.handle, L.ptr(theta), L.ptr(temp), C, L.ptr(rows), _stream(self.device)),
                 "ey_log_lik_rows")
         return rows
+
+    def forward(self, theta):
+        """[C, N, dK]: the network outputs of every chain's parameters on the attached batch, after the last activation
+        (ey_forward).  Any likelihood, any prior; the generic kernels or the layerwise forward products, whatever family
+        serves the plan's draws (``kernel`` is unchanged)."""
+        C = self._theta(theta)
+        out = self.empty(C, self.N, self.dims[-1])
+        L.check(L.lib().ey_forward(self.handle, L.ptr(theta), C, L.ptr(out), _stream(self.device)), "ey_forward")
+        return out
 
     def log_target_grad(self, theta, temp=None):
         C = self._theta(theta)

@@ -44,7 +44,24 @@ enum ey_act { EY_ACT_NONE = 0, EY_ACT_SIGMOID = 1, EY_ACT_TANH = 2, EY_ACT_RELU 
 /* likelihood codes: eeyore/constants/constants.py:15-18 */
 enum ey_lik {
   EY_LIK_BCE_SUM = 0, /* 'binary_classification': naive BCE(sum) on probabilities, eeyore/stats/loss.py:1-11 */
-  EY_LIK_CE_SUM = 1   /* 'multiclass_classification': CrossEntropyLoss(sum)(logits, argmax(y,1)) */
+  EY_LIK_CE_SUM = 1,  /* 'multiclass_classification': CrossEntropyLoss(sum)(logits, argmax(y,1)) */
+  /* Regression on a continuous or count response: BayesianModel takes any callable as loss, log_lik = -loss(forward(x), y)
+   * (eeyore/models/bayesian_model.py:30-35).  out = the network output after the last layer's activation (any supported
+   * activation), r = out - y, s = the plan's likelihood scale (ey_plan_set_lik_scale); the row term is summed over the
+   * d_K outputs:
+   *   EY_LIK_GAUSS_SUM    -log(s sqrt(2 pi)) - r^2 / (2 s^2)    = Normal(out, s).log_prob(y).sum()
+   *   EY_LIK_LAPLACE_SUM  -log(2 s) - |r| / s                   = Laplace(out, s).log_prob(y).sum(); the gradient takes
+   *                                                               sign(0) = 0, what autograd gives at the kink
+   *   EY_LIK_POISSON_SUM  y out - exp(out)                      = -PoissonNLLLoss(log_input=True, full=False,
+   *                                                               reduction='sum')(out, y): out is the log-rate and the
+   *                                                               y! term is left out, so this is the log-density of y up
+   *                                                               to a constant in y (no constant in theta is missing)
+   * Nothing is clamped: an exp that overflows gives a -inf or NaN target, which every accept step rejects, as the naive
+   * logs of the classification losses do.  A plan of these codes is served by the "generic" kernels or by "bgemm" (the
+   * separate layerwise launches); the fused families carry the classification losses only. */
+  EY_LIK_GAUSS_SUM = 2,
+  EY_LIK_LAPLACE_SUM = 3,
+  EY_LIK_POISSON_SUM = 4
 };
 
 enum ey_dtype { EY_F32 = 0, EY_F64 = 1 }; /* model.dtype, eeyore/models/model.py:7-10 */
@@ -118,7 +135,8 @@ int ey_plan_set_option(ey_plan* plan, int option, int value);
 int ey_plan_get_option(const ey_plan* plan, int option, int* value);
 
 /* The (x, y) full batch the samplers receive from their DataLoader (eeyore/samplers/serial_sampler.py:41-46).
- * x [N, d_0]; y [N, d_K] (one-hot for CE as XYDataset(yonehot=True) yields, {0,1} for BCE).  Copied into the plan. */
+ * x [N, d_0]; y [N, d_K] (one-hot for CE as XYDataset(yonehot=True) yields, {0,1} for BCE, the responses for the
+ * regression codes: counts for EY_LIK_POISSON_SUM).  Copied into the plan. */
 int ey_plan_set_data(ey_plan* plan, const void* x, const void* y, int64_t N, void* stream);
 /* model.prior = Normal(mu, sigma) elementwise (eeyore/models/mlp.py:31-35).  mu, sigma [P].  Copied. */
 int ey_plan_set_prior(ey_plan* plan, const void* mu, const void* sigma, void* stream);
@@ -139,6 +157,12 @@ int ey_plan_set_prior(ey_plan* plan, const void* mu, const void* sigma, void* st
 enum ey_prior_family { EY_PRIOR_NORMAL = 0, EY_PRIOR_LAPLACE = 1, EY_PRIOR_STUDENT_T = 2 };
 int ey_plan_set_prior_family(ey_plan* plan, int family, const void* loc, const void* scale, const void* df, void* stream);
 int ey_plan_prior_family(const ey_plan* plan);
+/* The scale s of EY_LIK_GAUSS_SUM / EY_LIK_LAPLACE_SUM: one positive number per plan (default 1), shared by the d_K outputs.
+ * The constants the kernels use (1/s^2 or 1/s, and the per-element log-normaliser) are worked out here in double and rounded
+ * once to the plan's dtype.  EY_ERR_INVALID: s not finite or not > 0, or a plan of a classification or Poisson code (which
+ * have no scale).  ey_plan_lik_scale returns s (1 for the codes without one). */
+int ey_plan_set_lik_scale(ey_plan* plan, double s);
+double ey_plan_lik_scale(const ey_plan* plan);
 
 /* BayesianModel.log_lik / log_prior / log_target (eeyore/models/bayesian_model.py:30-56) for C chains.
  * temp: per-chain temperature [C] or NULL (model.temperature = None); multiplies BOTH outputs (:33-34,48-49).
@@ -151,6 +175,14 @@ int ey_log_target(ey_plan* plan, const void* theta, const void* temp, int64_t C,
  * (eeyore/models/bayesian_model.py:58-67: exp of the log-likelihood of ONE point, averaged over samples by MCIntegrator,
  * eeyore/integrators/mcintegrator.py:16-36). */
 int ey_log_lik_rows(ey_plan* plan, const void* theta, const void* temp, int64_t C, void* rows, void* stream);
+/* MLP.forward (eeyore/models/mlp.py:45-50) of C parameter vectors on the attached batch: out [C, N, d_K] of the plan's
+ * dtype, out[c, n, :] = the network output of row n under theta[c] after the last layer's activation (logits under CE-sum,
+ * probabilities under BCE-sum, the mean / location / log-rate under the regression codes).  Any likelihood code, any prior
+ * family; data and prior must be attached (the y of the batch is not read into the result).  One launch of the generic
+ * kernels when the model fits their LDS image, the layerwise forward products otherwise -- also for a model that "mfma32"
+ * or "fused16" serves: the fused families have no such output, and ey_plan_kernel is unchanged by the call.
+ * EY_ERR_INVALID on a mixture plan (it has no network). */
+int ey_forward(ey_plan* plan, const void* theta, int64_t C, void* out, void* stream);
 /* LogTargetModel.upto_grad_log_target (eeyore/models/log_target_model.py:15-23): target [C], grad [C,P]. */
 int ey_log_target_grad(ey_plan* plan, const void* theta, const void* temp, int64_t C, void* target, void* grad,
                        void* stream);
