@@ -62,6 +62,33 @@ __device__ inline T dact_fn(int code, T h) {
   }
 }
 
+// The per-output likelihood terms, written once for tiny_rows and eval_target (the arithmetic is the same by construction).
+// They, and the steps the kernels share further down, are macros in the style of EY_LANE_PASS below: this compiler schedules
+// and allocates a kernel differently around an inlined function, and a macro leaves its code as it was.
+// EY_REG_TERM: one output's term of a regression log-likelihood and its derivative in the output (include/eeyore_amd.h:
+// enum ey_lik): r = out - y, lw = 1/s^2 or 1/s, lc the log-normaliser of one output.  `lik` is a kernel argument: the
+// branches are scalar.  It DECLARES the two names the caller passes as `term` and `d` (so it stands where a declaration
+// may) and leaves nothing else in the caller's scope; beside its arguments it reads T alone.
+#define EY_REG_TERM(lik, o, yy, lw, lc, term, d)                                                                     \
+  T term, d;                                                                                                         \
+  do {                                                                                                               \
+    const T ey_r_ = (o) - (yy);                                                                                      \
+    if ((lik) == EY_LIK_GAUSS_SUM) {                                                                                 \
+      term = (lc) - T(0.5) * ey_r_ * ey_r_ * (lw);                                                                   \
+      d = -ey_r_ * (lw);                                                                                             \
+    } else if ((lik) == EY_LIK_LAPLACE_SUM) {                                                                        \
+      term = (lc) - Num<T>::abs(ey_r_) * (lw);                                                                       \
+      d = ey_r_ > T(0) ? -(lw) : (ey_r_ < T(0) ? (lw) : T(0)); /* -sign(r) / s with sign(0) = 0 */                   \
+    } else { /* EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped (an overflowing exp gives a -inf target) */ \
+      const T ey_e_ = Num<T>::exp(o);                                                                                \
+      term = (yy) * (o) - ey_e_;                                                                                     \
+      d = (yy) - ey_e_;                                                                                              \
+    }                                                                                                                \
+  } while (0)
+
+// ... and of the BCE sum: naive logs exactly as eeyore/stats/loss.py:2 (NaN once a sigmoid saturates)
+#define EY_BCE_TERM(o, yy) (Num<T>::log(o) * (yy) + Num<T>::log(T(1) - (o)) * (T(1) - (yy)))
+#define EY_BCE_DOUT(o, yy) ((yy) / (o) - (T(1) - (yy)) / (T(1) - (o)))
 // A lane-strided pass over n elements with the SAME trip count in every lane: index i = lane + 64 k clamped to n - 1, `on`
 // saying whether the lane's element exists.  A lane beyond n in the last round repeats the work of element n - 1's owner --
 // the same inputs, hence the same bits to the same address -- and must keep its terms out of sums (select the term's
@@ -306,19 +333,7 @@ __device__ __forceinline__ T tiny_rows(const EyModel& m, const T* th, T* gr, boo
         if (j < dK) {
           const T o = out[j];
           const T yy = valid ? y[(size_t)n * dK + j] : T(0);
-          const T r = o - yy;
-          T term, dd;
-          if (m.lik == EY_LIK_GAUSS_SUM) {
-            term = lc - T(0.5) * r * r * lw;
-            dd = -r * lw;
-          } else if (m.lik == EY_LIK_LAPLACE_SUM) {
-            term = lc - Num<T>::abs(r) * lw;
-            dd = r > T(0) ? -lw : (r < T(0) ? lw : T(0));  // -sign(r) / s with sign(0) = 0
-          } else {  // EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped (an overflowing exp gives a -inf target)
-            const T e = Num<T>::exp(o);
-            term = yy * o - e;
-            dd = yy - e;
-          }
+          EY_REG_TERM(m.lik, o, yy, lw, lc, term, dd);
           lik += valid ? term : T(0);
           row_lik += term;
           if (GRAD) d[j] = valid ? dd * dact_fn<T>(act_out, o) : T(0);
@@ -330,11 +345,11 @@ __device__ __forceinline__ T tiny_rows(const EyModel& m, const T* th, T* gr, boo
         if (j < dK) {
           const T o = out[j];
           const T yy = valid ? y[(size_t)n * dK + j] : T(0);
-          const T term = Num<T>::log(o) * yy + Num<T>::log(T(1) - o) * (T(1) - yy);
+          const T term = EY_BCE_TERM(o, yy);
           lik += valid ? term : T(0);
           row_lik += term;
           if (GRAD) {
-            const T dd = (yy / o - (T(1) - yy) / (T(1) - o)) * dact_fn<T>(act_out, o);
+            const T dd = EY_BCE_DOUT(o, yy) * dact_fn<T>(act_out, o);
             d[j] = valid ? dd : T(0);
           }
         }
@@ -639,19 +654,7 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
       for (int j = 0; j < dK; ++j) {
         const T o = out[j * TS];
         const T yy = valid ? y[(size_t)n * dK + j] : T(0);
-        const T r = o - yy;
-        T term, d;
-        if (m.lik == EY_LIK_GAUSS_SUM) {
-          term = lc - T(0.5) * r * r * lw;
-          d = -r * lw;
-        } else if (m.lik == EY_LIK_LAPLACE_SUM) {
-          term = lc - Num<T>::abs(r) * lw;
-          d = r > T(0) ? -lw : (r < T(0) ? lw : T(0));  // -sign(r) / s with sign(0) = 0
-        } else {  // EY_LIK_POISSON_SUM: out is the log-rate; nothing clamped
-          const T e = Num<T>::exp(o);
-          term = yy * o - e;
-          d = yy - e;
-        }
+        EY_REG_TERM(m.lik, o, yy, lw, lc, term, d);
         if (valid) lik += term;
         row_lik += term;
         if (GRAD) dcur[j * TS + lane] = valid ? d * dact_fn<T>(m.act[nl - 1], o) : T(0);
@@ -662,11 +665,11 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
         const T o = out[j * TS];
         const T yy = valid ? y[(size_t)n * dK + j] : T(0);
         // naive logs exactly as eeyore/stats/loss.py:2 (NaN once a sigmoid saturates)
-        const T term = Num<T>::log(o) * yy + Num<T>::log(T(1) - o) * (T(1) - yy);
+        const T term = EY_BCE_TERM(o, yy);
         if (valid) lik += term;
         row_lik += term;
         if (GRAD) {
-          const T d = (yy / o - (T(1) - yy) / (T(1) - o)) * dact_fn<T>(m.act[nl - 1], o);
+          const T d = EY_BCE_DOUT(o, yy) * dact_fn<T>(m.act[nl - 1], o);
           dcur[j * TS + lane] = valid ? d : T(0);
         }
       }
@@ -796,13 +799,62 @@ __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
   return lik + prior;
 }
 
+// ----------------------------------------------------------------------------------------------- steps the kernels share
+// Each is written once and expanded where a kernel takes it; what a kernel does differently it passes in.
+// Beside its arguments a macro reads names that every kernel using it gives its template parameters, arguments and
+// locals; each macro's comment lists the names it reads.  Those that are statements are used with a semicolon.
+
+// How a row-wave kernel starts: the wave's place among the chain's waves (rw) and its own LDS image of nvec [P] vectors (l).
+// RW false: one wave, all of this folds away.  Wave 0 is the wave that writes to global memory (ROW WAVES).
+// DECLARES smem, rw and l for the kernel.  Reads: T, RW, m.
+#define EY_WAVE_IMAGE(nvec)                                                                             \
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];                                  \
+  const RowWaves rw = RW ? row_waves<T>(m, smem, nvec) : RowWaves{0, 1, nullptr};                       \
+  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, nvec, sizeof(T)) : 0), nvec)
+
+// The leapfrog trajectory (hmc.py:100-124) from the gradient in l.gr: half a momentum step, L position steps with an
+// evaluation each (its value left in t), the last momentum step halved; grad_potential = -grad.
+// Reads: T, TINY, m, l, rw, lane, P, p (the momentum, in LDS), eps, L, ht, tc.
+#define EY_LEAPFROG(t)                                                                         \
+  do {                                                                                         \
+    for (int i = lane; i < P; i += WAVE) p[i] = p[i] + T(0.5) * eps * l.gr[i];                 \
+    for (int k = 1; k <= L; ++k) {                                                             \
+      for (int i = lane; i < P; i += WAVE) l.th[i] = l.th[i] + eps * p[i];                     \
+      t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr, nullptr, rw); \
+      const T w = (k < L) ? eps : T(0.5) * eps;                                                \
+      for (int i = lane; i < P; i += WAVE) p[i] = p[i] + w * l.gr[i];                          \
+    }                                                                                          \
+  } while (0)
+
+// What a draw leaves behind.  By the wave that writes (`on`): the recorded sample `value` of element i, the state the chain
+// is left in (what ChainList.update stores, chain_list.py:64-67) ...  Reads: T, run, it, C, c, P, lane.
+#define EY_RECORD_SAMPLE(on, i, value)                                  \
+  do {                                                                  \
+    if (run.samples && (on)) {                                          \
+      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P; \
+      for (int i = lane; i < P; i += WAVE) so[i] = (value);             \
+    }                                                                   \
+  } while (0)
+// ... and by its lane 0 (`on`): the state's target, the accept flag, the log-rate and the run's records.  (A
+// function: this one the compiler inlines without a trace.)
+template <typename T>
+__device__ __forceinline__ void record_draw(bool on, int64_t c, int it, int64_t C, bool acc, T tv, T t_state, T log_rate,
+                                            T* target, unsigned char* accepted, T* log_rate_o, const EyRun& run) {
+  if (on) {
+    if (acc) target[c] = tv;
+    accepted[c] = acc ? 1 : 0;
+    if (log_rate_o) log_rate_o[c] = log_rate;
+    if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
+    if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc ? 1 : 0;
+    if (run.accept_count && acc) run.accept_count[c] += 1;
+  }
+}
+
 // ----------------------------------------------------------------------------------------------- kernels
 template <typename T, bool GRAD, class TINY, bool RW = false>
 __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_log_target(EyModel m, const T* theta, const T* temp, T* lik_o, T* prior_o,
                                                      T* target_o, T* grad_o, T* rows_o) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 2) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 2, sizeof(T)) : 0), 2);
+  EY_WAVE_IMAGE(2);
   const bool w0 = rw.wave == 0;  // the wave that writes to global memory (ROW WAVES)
   const int64_t c = blockIdx.x;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -826,15 +878,16 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_log_target(EyMode
 // evaluation also works out are dropped.
 template <typename T, class TINY, bool RW = false>
 __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_forward(EyModel m, const T* theta, T* out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 2) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 2, sizeof(T)) : 0), 2);
+  EY_WAVE_IMAGE(2);
   const int64_t c = blockIdx.x;
   const int lane = threadIdx.x & (WAVE - 1);
   for (int i = lane; i < m.P; i += WAVE) l.th[i] = theta[c * m.P + i];
   eval_target<T, false, TINY>(m, l, l.th, l.gr, false, T(1), nullptr, nullptr, nullptr, rw, out + c * m.N * m.dims[m.nl]);
 }
 
+// k_hmc takes an EyRun's fields as five arguments of its own and keeps its own record of a draw (EY_RECORD_SAMPLE and
+// record_draw read an EyRun): handing it the struct changes the instructions of every one of its instantiations, and
+// k_hmc<double, TinyDyn> sits at 512 registers with scratch.
 template <typename T, class TINY, bool RW = false>
 __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_hmc(EyModel m, T* theta, T* target, T* grad, const T* p0, const T* u_in,
                                               T step, const T* step_vec, int L, const T* temp, uint64_t seed,
@@ -842,9 +895,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_hmc(EyModel m, T*
                                               unsigned char* accepted, T* rate_o, T* hcur_o, T* hprop_o, int n_iters,
                                               T* rec_samples, T* rec_targets, unsigned char* rec_accepted,
                                               int* accept_count, int64_t C) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 3) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 3, sizeof(T)) : 0), 3);
+  EY_WAVE_IMAGE(3);
   const bool w0 = rw.wave == 0;  // the wave that writes to global memory (ROW WAVES)
   const int64_t c = blockIdx.x;
   const int lane = RW ? (threadIdx.x & (WAVE - 1)) : threadIdx.x;
@@ -876,14 +927,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_hmc(EyModel m, T*
   __syncthreads();
   T t = t_cur;
   if (recompute) t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr, nullptr, rw);  // hmc.py:104
-  // leapfrog (hmc.py:100-124); grad_potential = -grad
-  for (int i = lane; i < P; i += WAVE) p[i] = p[i] + T(0.5) * eps * l.gr[i];
-  for (int k = 1; k <= L; ++k) {
-    for (int i = lane; i < P; i += WAVE) l.th[i] = l.th[i] + eps * p[i];
-    t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr, nullptr, rw);
-    const T w = (k < L) ? eps : T(0.5) * eps;
-    for (int i = lane; i < P; i += WAVE) p[i] = p[i] + w * l.gr[i];
-  }
+  EY_LEAPFROG(t);
   kin = T(0);
   EY_LANE_PASS(P, i, on) {  // p -> -p leaves it unchanged (hmc.py:122)
     const T pz = on ? p[i] : T(0);
@@ -925,9 +969,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_hmc(EyModel m, T*
 template <typename T, class TINY, bool RW = false>
 __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_leapfrog(EyModel m, T* theta, T* pio, T step, const T* step_vec, int L,
                                                    const T* temp, T* target, T* grad) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 3) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 3, sizeof(T)) : 0), 3);
+  EY_WAVE_IMAGE(3);
   const bool w0 = rw.wave == 0;  // the wave that writes to global memory (ROW WAVES)
   const int64_t c = blockIdx.x;
   const int lane = RW ? (threadIdx.x & (WAVE - 1)) : threadIdx.x;
@@ -942,13 +984,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_leapfrog(EyModel 
   }
   __syncthreads();
   T t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr, nullptr, rw);
-  for (int i = lane; i < P; i += WAVE) p[i] = p[i] + T(0.5) * eps * l.gr[i];
-  for (int k = 1; k <= L; ++k) {
-    for (int i = lane; i < P; i += WAVE) l.th[i] = l.th[i] + eps * p[i];
-    t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr, nullptr, rw);
-    const T w = (k < L) ? eps : T(0.5) * eps;
-    for (int i = lane; i < P; i += WAVE) p[i] = p[i] + w * l.gr[i];
-  }
+  EY_LEAPFROG(t);
   if (w0) {
     for (int i = lane; i < P; i += WAVE) {
       theta[c * P + i] = l.th[i];
@@ -964,9 +1000,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_mala(EyModel m, T
                                                T step, T sqrt_step, const T* step_vec, const T* temp, uint64_t seed,
                                                uint64_t iter0, uint64_t chain_offset, unsigned char* accepted,
                                                T* log_rate_o, EyRun run, int64_t C) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 4) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 4, sizeof(T)) : 0), 4);
+  EY_WAVE_IMAGE(4);
   const bool w0 = rw.wave == 0;  // the wave that writes to global memory (ROW WAVES)
   const int64_t c = blockIdx.x;
   const int lane = RW ? (threadIdx.x & (WAVE - 1)) : threadIdx.x;
@@ -1020,18 +1054,8 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_mala(EyModel m, T
         grad[c * P + i] = gp[i];
       }
   }
-  if (run.samples && w0) {  // the state the chain is left in (what ChainList.update stores, chain_list.py:64-67)
-    T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-    for (int i = lane; i < P; i += WAVE) so[i] = acc ? prop[i] : l.th[i];
-  }
-  if (lane == 0 && w0) {
-    if (acc) target[c] = tv;
-    accepted[c] = acc ? 1 : 0;
-    if (log_rate_o) log_rate_o[c] = log_rate;
-    if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-    if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc ? 1 : 0;
-    if (run.accept_count && acc) run.accept_count[c] += 1;
-  }
+  EY_RECORD_SAMPLE(w0, i, acc ? prop[i] : l.th[i]);
+  record_draw<T>(lane == 0 && w0, c, it, C, acc, tv, t_state, log_rate, target, accepted, log_rate_o, run);
   __syncthreads();
   }
 }
@@ -1041,9 +1065,7 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_mh(EyModel m, T* 
                                              const T* scale, const T* temp, uint64_t seed, uint64_t iter0,
                                              uint64_t chain_offset, unsigned char* accepted, T* log_rate_o, EyRun run,
                                              int64_t C) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const RowWaves rw = RW ? row_waves<T>(m, smem, 2) : RowWaves{0, 1, nullptr};  // RW false: one wave, all of this folds away
-  const Lds<T> l = carve<T>(m, smem + (RW ? (size_t)rw.wave * lds_bytes(m, 2, sizeof(T)) : 0), 2);
+  EY_WAVE_IMAGE(2);
   const bool w0 = rw.wave == 0;  // the wave that writes to global memory (ROW WAVES)
   const int64_t c = blockIdx.x;
   const int lane = RW ? (threadIdx.x & (WAVE - 1)) : threadIdx.x;
@@ -1070,18 +1092,8 @@ __global__ void __launch_bounds__(RW ? RW_MAX * WAVE : WAVE) k_mh(EyModel m, T* 
     if (w0)
       for (int i = lane; i < P; i += WAVE) theta[c * P + i] = l.th[i];
   }
-  if (run.samples && w0) {
-    T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-    for (int i = lane; i < P; i += WAVE) so[i] = acc ? l.th[i] : theta[c * P + i];
-  }
-  if (lane == 0 && w0) {
-    if (acc) target[c] = tv;
-    accepted[c] = acc ? 1 : 0;
-    if (log_rate_o) log_rate_o[c] = log_rate;
-    if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-    if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc ? 1 : 0;
-    if (run.accept_count && acc) run.accept_count[c] += 1;
-  }
+  EY_RECORD_SAMPLE(w0, i, acc ? l.th[i] : theta[c * P + i]);
+  record_draw<T>(lane == 0 && w0, c, it, C, acc, tv, t_state, log_rate, target, accepted, log_rate_o, run);
   __syncthreads();
   }
 }
@@ -1131,13 +1143,9 @@ static int tiny_dispatch(const ey_plan* pl, F f) {
   if (pl->m.kind == EY_KIND_MIX) return f(TargetMix{});
   return tiny_dispatch_mlp(pl, f);
 }
-#define EY_TINY_DISPATCH_MLP(fn, ...)                                                                  \
-  tiny_dispatch_mlp(pl, [&](auto tiny_tag) {                                                           \
-    typedef decltype(tiny_tag) TinyS;                                                                  \
-    return pl->dtype == EY_F32 ? fn<float, TinyS>(__VA_ARGS__) : fn<double, TinyS>(__VA_ARGS__);       \
-  })
-#define EY_TINY_DISPATCH(fn, ...)                                                                      \
-  tiny_dispatch(pl, [&](auto tiny_tag) {                                                               \
+// fn<T, policy>(...) for the plan's dtype and the policy `dispatch` (tiny_dispatch or tiny_dispatch_mlp) picks
+#define EY_TINY_DISPATCH(dispatch, fn, ...)                                                            \
+  dispatch(pl, [&](auto tiny_tag) {                                                                    \
     typedef decltype(tiny_tag) TinyS;                                                                  \
     return pl->dtype == EY_F32 ? fn<float, TinyS>(__VA_ARGS__) : fn<double, TinyS>(__VA_ARGS__);       \
   })
@@ -1151,64 +1159,60 @@ static int prep(K kernel, size_t bytes) {
   return EY_OK;
 }
 
-// the kernels' row-waves instantiation (RW) where the launch uses several waves per chain, the lean one otherwise
-template <class TINY, typename F>
-static int with_row_waves(int nw, F f) {
-  if constexpr (TINY::on) {
-    if (nw > 1) return f(std::true_type{});
-  }
-  return f(std::false_type{});
+// one draw, nothing recorded: the run of a caller that passes none
+static const EyRun kOneDraw = {1, nullptr, nullptr, nullptr, nullptr};
+
+// one kernel over C chains of nw waves: the LDS attribute, the launch, its error
+template <typename... Ps, typename... As>
+static int launch(void (*kernel)(Ps...), int64_t C, int nw, size_t bytes, hipStream_t s, As... args) {
+  int rc;
+  if ((rc = prep(kernel, bytes))) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)C), dim3(nw * WAVE), bytes, s, args...);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
 }
+// ... of a row-wave kernel with an image of nvec vectors: its row-waves instantiation (RW) where the launch uses several
+// waves per chain, the lean one otherwise.  kernel_of(std::bool_constant<RW>) names the instantiation (EY_RW_KERNEL).
+template <typename T, class TINY, typename KF, typename... As>
+static int launch_row_waves(ey_plan* pl, int nvec, int64_t C, hipStream_t s, KF kernel_of, As... args) {
+  const int nw = row_waves_for(pl, TINY::on, C);
+  const size_t bytes = lds_total(pl->m, nvec, sizeof(T), nw);
+  if constexpr (TINY::on) {
+    if (nw > 1) return launch(kernel_of(std::true_type{}), C, nw, bytes, s, args...);
+  }
+  return launch(kernel_of(std::false_type{}), C, nw, bytes, s, args...);
+}
+#define EY_RW_KERNEL(k, ...) [](auto rw_tag) { return k<__VA_ARGS__, decltype(rw_tag)::value>; }
 
 template <typename T, class TINY>
 static int launch_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                              void* target, void* grad, hipStream_t s, void* rows = nullptr) {
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 2, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if (grad) {
-      if ((rc = prep(k_log_target<T, true, TINY, RW>, bytes))) return rc;
-      hipLaunchKernelGGL((k_log_target<T, true, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m,
-                         (const T*)theta, (const T*)temp, (T*)lik, (T*)prior, (T*)target, (T*)grad, (T*)nullptr);
-    } else {
-      if ((rc = prep(k_log_target<T, false, TINY, RW>, bytes))) return rc;
-      hipLaunchKernelGGL((k_log_target<T, false, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m,
-                         (const T*)theta, (const T*)temp, (T*)lik, (T*)prior, (T*)target, (T*)nullptr, (T*)rows);
-    }
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  if (grad)
+    return launch_row_waves<T, TINY>(pl, 2, C, s, EY_RW_KERNEL(k_log_target, T, true, TINY), pl->m, (const T*)theta,
+                                     (const T*)temp, (T*)lik, (T*)prior, (T*)target, (T*)grad, (T*)nullptr);
+  return launch_row_waves<T, TINY>(pl, 2, C, s, EY_RW_KERNEL(k_log_target, T, false, TINY), pl->m, (const T*)theta,
+                                   (const T*)temp, (T*)lik, (T*)prior, (T*)target, (T*)nullptr, (T*)rows);
 }
 
 int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                           void* target, void* grad, hipStream_t s) {
-  return EY_TINY_DISPATCH(launch_log_target, pl, theta, temp, C, lik, prior, target, grad, s);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_log_target, pl, theta, temp, C, lik, prior, target, grad, s);
 }
 
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s) {
   if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: this plan has no data rows");
-  return EY_TINY_DISPATCH(launch_log_target, pl, theta, temp, C, nullptr, nullptr, nullptr, nullptr, s, rows);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_log_target, pl, theta, temp, C, nullptr, nullptr, nullptr, nullptr, s,
+                          rows);
 }
 
 template <typename T, class TINY>
 static int launch_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 2, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if ((rc = prep(k_forward<T, TINY, RW>, bytes))) return rc;
-    hipLaunchKernelGGL((k_forward<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (const T*)theta, (T*)out);
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  return launch_row_waves<T, TINY>(pl, 2, C, s, EY_RW_KERNEL(k_forward, T, TINY), pl->m, (const T*)theta, (T*)out);
 }
 // ey_forward: out [C, N, dK]
 int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s) {
   if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_INVALID, "ey_forward: this plan has no network");
-  return EY_TINY_DISPATCH_MLP(launch_forward, pl, theta, C, out, s);
+  return EY_TINY_DISPATCH(tiny_dispatch_mlp, launch_forward, pl, theta, C, out, s);
 }
 
 template <typename T, class TINY>
@@ -1216,103 +1220,65 @@ static int launch_hmc(ey_plan* pl, void* theta, void* target, void* grad, const 
                       const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                       uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
                       hipStream_t s, const EyRun* run) {
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 3, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if ((rc = prep(k_hmc<T, TINY, RW>, bytes))) return rc;
-    hipLaunchKernelGGL((k_hmc<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (T*)theta, (T*)target, (T*)grad,
-                       (const T*)p0, (const T*)u, (T)step, (const T*)step_vec, L, (const T*)temp, seed, iter,
-                       chain_offset, (int)((flags & EY_RECOMPUTE_INITIAL_GRAD) != 0), (unsigned char*)accepted, (T*)rate,
-                       (T*)hcur, (T*)hprop, run ? run->n_iters : 1, run ? (T*)run->samples : nullptr,
-                       run ? (T*)run->targets : nullptr, run ? (unsigned char*)run->accepted : nullptr,
-                       run ? run->accept_count : nullptr, C);
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  return launch_row_waves<T, TINY>(pl, 3, C, s, EY_RW_KERNEL(k_hmc, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
+                                   (const T*)p0, (const T*)u, (T)step, (const T*)step_vec, L, (const T*)temp, seed, iter,
+                                   chain_offset, (int)((flags & EY_RECOMPUTE_INITIAL_GRAD) != 0), (unsigned char*)accepted,
+                                   (T*)rate, (T*)hcur, (T*)hprop, run ? run->n_iters : 1, run ? (T*)run->samples : nullptr,
+                                   run ? (T*)run->targets : nullptr, run ? (unsigned char*)run->accepted : nullptr,
+                                   run ? run->accept_count : nullptr, C);
 }
 
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
                    const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                    uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
                    hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(launch_hmc, pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset,
-                                 flags, accepted, rate, hcur, hprop, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc, pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed,
+                          iter, chain_offset, flags, accepted, rate, hcur, hprop, s, run);
 }
 
 template <typename T, class TINY>
 static int launch_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                            int64_t C, void* target, void* grad, hipStream_t s) {
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 3, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if ((rc = prep(k_leapfrog<T, TINY, RW>, bytes))) return rc;
-    hipLaunchKernelGGL((k_leapfrog<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (T*)theta, (T*)p, (T)step,
-                       (const T*)step_vec, L, (const T*)temp, (T*)target, (T*)grad);
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  return launch_row_waves<T, TINY>(pl, 3, C, s, EY_RW_KERNEL(k_leapfrog, T, TINY), pl->m, (T*)theta, (T*)p, (T)step,
+                                   (const T*)step_vec, L, (const T*)temp, (T*)target, (T*)grad);
 }
 
 int ey_generic_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                         int64_t C, void* target, void* grad, hipStream_t s) {
-  return EY_TINY_DISPATCH(launch_leapfrog, pl, theta, p, step, step_vec, L, temp, C, target, grad, s);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_leapfrog, pl, theta, p, step, step_vec, L, temp, C, target, grad, s);
 }
 
 template <typename T, class TINY>
 static int launch_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
                        const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                        uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 4, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if ((rc = prep(k_mala<T, TINY, RW>, bytes))) return rc;
-    // scale = np.sqrt(step) on the python float, then cast to the model dtype (mala.py:39)
-    hipLaunchKernelGGL((k_mala<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (T*)theta, (T*)target, (T*)grad,
-                       (const T*)z, (const T*)u, (T)step, (T)sqrt(step), (const T*)step_vec, (const T*)temp, seed, iter,
-                       chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : one, C);
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  // scale = np.sqrt(step) on the python float, then cast to the model dtype (mala.py:39)
+  return launch_row_waves<T, TINY>(pl, 4, C, s, EY_RW_KERNEL(k_mala, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
+                                   (const T*)z, (const T*)u, (T)step, (T)sqrt(step), (const T*)step_vec, (const T*)temp, seed,
+                                   iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
 int ey_generic_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
                     const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                     uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(launch_mala, pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter,
-                                                  chain_offset, accepted, log_rate, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mala, pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter,
+                          chain_offset, accepted, log_rate, s, run);
 }
 
 template <typename T, class TINY>
 static int launch_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
                      const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
                      void* log_rate, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const int nw = row_waves_for(pl, TINY::on, C);
-  const size_t bytes = lds_total(pl->m, 2, sizeof(T), nw);
-  return with_row_waves<TINY>(nw, [&](auto rwtag) -> int {
-    constexpr bool RW = decltype(rwtag)::value;
-    int rc;
-    if ((rc = prep(k_mh<T, TINY, RW>, bytes))) return rc;
-    hipLaunchKernelGGL((k_mh<T, TINY, RW>), dim3((unsigned)C), dim3(nw * WAVE), bytes, s, pl->m, (T*)theta, (T*)target, (const T*)z,
-                       (const T*)u, (const T*)scale, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted,
-                       (T*)log_rate, run ? *run : one, C);
-    EY_HIP(hipGetLastError());
-    return (int)EY_OK;
-  });
+  return launch_row_waves<T, TINY>(pl, 2, C, s, EY_RW_KERNEL(k_mh, T, TINY), pl->m, (T*)theta, (T*)target, (const T*)z,
+                                   (const T*)u, (const T*)scale, (const T*)temp, seed, iter, chain_offset,
+                                   (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
 int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
                   const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
                   void* log_rate, hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(launch_mh, pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset,
-                                                accepted, log_rate, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh, pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset,
+                          accepted, log_rate, s, run);
 }
 
 // ----------------------------------------------------------------------------------------------- robust adaptive Metropolis
@@ -1334,6 +1300,48 @@ __host__ __device__ static size_t ram_extra_bytes(int P, size_t esz) {
   return esz * (packed + 3 * Ppad + WAVE);  // factor, w, d, g, and a slot per lane for the stores of rows above a column
 }
 
+// ---- steps the one-wave kernels share (k_ram, k_mh_tril, k_mala_tril, k_am, k_gibbs), macros as the kernels' above
+// Lg: chain c's factor in tril [G, P, P], chosen as the comment of k_mh_tril says (G, tril_index, clamped into [0, G)).
+// DECLARES g and Lg.  Reads: T, tril, tril_index, G, c, P.
+#define EY_CHAIN_FACTOR(Lg)                                           \
+  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c); \
+  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);                            \
+  const T* Lg = tril + g * (int64_t)P * P
+
+// z of a draw into the LDS vector dst: the chain's own stream, or the caller's values.  Reads: T, z_in, rn, c, P, lane.
+#define EY_READ_Z(dst)                                                 \
+  do {                                                                 \
+    if (!z_in) fill_normals<T>(dst, rn, P);                            \
+    else {                                                             \
+      for (int i = lane; i < P; i += WAVE) (dst)[i] = z_in[c * P + i]; \
+      __syncthreads();                                                 \
+    }                                                                  \
+  } while (0)
+
+// a dense row-major lower triangle (only j <= i is touched) into the packed ram_col order.  One statement.  Reads: P, lane.
+#define EY_TRIL_PACK(S, dense)                                                                        \
+  for (int j = 0; j < P; ++j)                                                                         \
+    for (int i = j + lane; i < P; i += WAVE) (S)[ram_col(j, P) + i - j] = (dense)[(int64_t)i * P + j]
+
+// acc[r] += sum_j (b S[i, j]) z[j] for the packed factor S and the lane's R rows i = lane + 64 r: a column sweep, one running
+// sum per row (clamped index, the term's input selected to zero: DESIGN.md 4.4).  R is wave-uniform (P <= 64 has no second
+// row); a caller without a scale passes b = 1, which multiplies nothing.  Reads: T, P, lane.
+#define EY_TRIL_SWEEP(S, z, R, b, acc)            \
+  do {                                            \
+    for (int j = 0; j < P; ++j) {                 \
+      const T zj = (z)[j];                        \
+      const T* col = (S) + ram_col(j, P) - j;     \
+      _Pragma("unroll")                           \
+      for (int r = 0; r < 2; ++r) {               \
+        if (r >= (R)) break;                      \
+        const int i = lane + r * WAVE;            \
+        const bool on = i >= j && i < P;          \
+        const T s = col[on ? i : j];              \
+        (acc)[r] += ((b) * (on ? s : T(0))) * zj; \
+      }                                           \
+    }                                             \
+  } while (0)
+
 template <typename T, class TINY>
 __global__ void __launch_bounds__(WAVE) k_ram(EyModel m, T* theta, T* target, T* chol, const T* z_in, const T* u_in,
                                               double a, double g, uint64_t n0, const T* temp, uint64_t seed,
@@ -1353,30 +1361,15 @@ __global__ void __launch_bounds__(WAVE) k_ram(EyModel m, T* theta, T* target, T*
   const bool ht = temp != nullptr;
   const T tc = ht ? temp[c] : T(1);
   T* Sg = chol + c * (int64_t)P * P;
-  for (int j = 0; j < P; ++j)
-    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Sg[(int64_t)i * P + j];
+  EY_TRIL_PACK(S, Sg);
   T t_state = target[c];
   for (int it = 0; it < run.n_iters; ++it) {
     const uint64_t iter = iter0 + (uint64_t)it;
     // ---- z ~ N(0, I) (ram.py:44), then the proposal theta + S z (:45): a column sweep, one running sum per row
     const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
-    if (!z_in) fill_normals<T>(w, rn, P);
-    else {
-      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
-      __syncthreads();
-    }
+    EY_READ_Z(w);
     T acc[2] = {T(0), T(0)};
-    for (int j = 0; j < P; ++j) {
-      const T zj = w[j];
-      const T* col = S + ram_col(j, P) - j;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int i = lane + r * WAVE;
-        const bool on = i >= j && i < P;
-        const T s = col[on ? i : j];
-        acc[r] += (on ? s : T(0)) * zj;
-      }
-    }
+    EY_TRIL_SWEEP(S, w, 2, T(1), acc);
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int i = lane + r * WAVE;
@@ -1392,18 +1385,8 @@ __global__ void __launch_bounds__(WAVE) k_ram(EyModel m, T* theta, T* target, T*
       t_state = tv;
       for (int i = lane; i < P; i += WAVE) theta[c * P + i] = l.th[i];
     }
-    if (run.samples) {
-      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? l.th[i] : theta[c * P + i];
-    }
-    if (lane == 0) {
-      if (acc_) target[c] = tv;
-      accepted[c] = acc_ ? 1 : 0;
-      if (log_rate_o) log_rate_o[c] = log_rate;
-      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
-      if (run.accept_count && acc_) run.accept_count[c] += 1;
-    }
+    EY_RECORD_SAMPLE(true, i, acc_ ? l.th[i] : theta[c * P + i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, tv, t_state, log_rate, target, accepted, log_rate_o, run);
     // ---- adaptation (:59-63), accepted or not.  alpha = min(1, exp(log_rate)) as Python's min takes it: NaN -> 1.
     const T e = Num<T>::exp(log_rate);
     const T alpha = e < T(1) ? e : T(1);
@@ -1459,23 +1442,30 @@ __global__ void __launch_bounds__(WAVE) k_ram(EyModel m, T* theta, T* target, T*
     }
     __syncthreads();
   }
-  for (int j = 0; j < P; ++j)
+  for (int j = 0; j < P; ++j)  // the adapted factor back to its dense form
     for (int i = j + lane; i < P; i += WAVE) Sg[(int64_t)i * P + j] = S[ram_col(j, P) + i - j];
+}
+
+// The two limits of the kernels that keep [P, P] triangles in LDS beside the evaluation image, under the sampler's name:
+// `lives` is what the P limit is for, `held` what the bytes hold.
+static int tril_limits(const ey_plan* pl, const std::string& name, const std::string& lives, const std::string& held,
+                       size_t bytes) {
+  if (pl->m.P > RAM_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, name + ": P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
+                                    std::to_string(RAM_MAX_P) + " parameters (" + lives + " lives in LDS)");
+  if (bytes > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, name + ": " + held + " and the model's evaluation image (" + std::to_string(bytes) +
+                                    " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_OK;
 }
 
 template <typename T, class TINY>
 static int launch_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a,
                       double g, uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes = ey_generic_ram_lds(pl);
-  int rc;
-  if ((rc = prep(k_ram<T, TINY>, bytes))) return rc;
-  hipLaunchKernelGGL((k_ram<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target, (T*)chol,
-                     (const T*)z, (const T*)u, a, g, n, (const T*)temp, seed, iter, chain_offset,
-                     (unsigned char*)accepted, (T*)log_rate, run ? *run : one, C);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  return launch(k_ram<T, TINY>, C, 1, ey_generic_ram_lds(pl), s, pl->m, (T*)theta, (T*)target, (T*)chol, (const T*)z,
+                (const T*)u, a, g, n, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
+                run ? *run : kOneDraw, C);
 }
 
 size_t ey_generic_ram_lds(const ey_plan* pl) {
@@ -1486,14 +1476,9 @@ size_t ey_generic_ram_lds(const ey_plan* pl) {
 int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                    void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  if (pl->m.P > RAM_MAX_P)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "RAM: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
-                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
-  if (ey_generic_ram_lds(pl) > 160 * 1024)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "RAM: the factor and the model's evaluation image (" +
-                                    std::to_string(ey_generic_ram_lds(pl)) + " bytes) do not fit the 160 KiB LDS of a CU");
-  return EY_TINY_DISPATCH(launch_ram, pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted,
-                          log_rate, s, run);
+  if (int rc = tril_limits(pl, "RAM", "the factor", "the factor", ey_generic_ram_lds(pl))) return rc;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_ram, pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter,
+                          chain_offset, accepted, log_rate, s, run);
 }
 
 // ----------------------------------------------------------------------------------------------- MH with a fixed factor
@@ -1524,33 +1509,16 @@ __global__ void __launch_bounds__(WAVE) k_mh_tril(EyModel m, T* theta, T* target
   const int lane = threadIdx.x;
   const bool ht = temp != nullptr;
   const T tc = ht ? temp[c] : T(1);
-  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c);
-  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
-  const T* Lg = tril + g * (int64_t)P * P;
-  for (int j = 0; j < P; ++j)
-    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Lg[(int64_t)i * P + j];
+  EY_CHAIN_FACTOR(Lg);
+  EY_TRIL_PACK(S, Lg);
   T t_state = target[c];
   for (int it = 0; it < run.n_iters; ++it) {  // ey_mh_tril_run: see k_mala
     const uint64_t iter = iter0 + (uint64_t)it;
     const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
-    if (!z_in) fill_normals<T>(w, rn, P);
-    else {
-      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
-      __syncthreads();
-    }
-    // theta + L z: k_ram's column sweep (clamped index, the term's input selected to zero: DESIGN.md 4.4)
+    EY_READ_Z(w);
+    // theta + L z: k_ram's column sweep
     T acc[2] = {T(0), T(0)};
-    for (int j = 0; j < P; ++j) {
-      const T zj = w[j];
-      const T* col = S + ram_col(j, P) - j;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int i = lane + r * WAVE;
-        const bool on = i >= j && i < P;
-        const T s = col[on ? i : j];
-        acc[r] += (on ? s : T(0)) * zj;
-      }
-    }
+    EY_TRIL_SWEEP(S, w, 2, T(1), acc);
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int i = lane + r * WAVE;
@@ -1566,18 +1534,8 @@ __global__ void __launch_bounds__(WAVE) k_mh_tril(EyModel m, T* theta, T* target
       t_state = tv;
       for (int i = lane; i < P; i += WAVE) theta[c * P + i] = l.th[i];
     }
-    if (run.samples) {
-      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? l.th[i] : theta[c * P + i];
-    }
-    if (lane == 0) {
-      if (acc_) target[c] = tv;
-      accepted[c] = acc_ ? 1 : 0;
-      if (log_rate_o) log_rate_o[c] = log_rate;
-      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
-      if (run.accept_count && acc_) run.accept_count[c] += 1;
-    }
+    EY_RECORD_SAMPLE(true, i, acc_ ? l.th[i] : theta[c * P + i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, tv, t_state, log_rate, target, accepted, log_rate_o, run);
     __syncthreads();
   }
 }
@@ -1586,15 +1544,9 @@ template <typename T, class TINY>
 static int launch_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                           const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                           uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes = ey_generic_mh_tril_lds(pl);
-  int rc;
-  if ((rc = prep(k_mh_tril<T, TINY>, bytes))) return rc;
-  hipLaunchKernelGGL((k_mh_tril<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
-                     (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (const T*)temp, seed, iter,
-                     chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : one, C);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  return launch(k_mh_tril<T, TINY>, C, 1, ey_generic_mh_tril_lds(pl), s, pl->m, (T*)theta, (T*)target, (const T*)tril, G,
+                (const int*)tril_index, (const T*)z, (const T*)u, (const T*)temp, seed, iter, chain_offset,
+                (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
 size_t ey_generic_mh_tril_lds(const ey_plan* pl) {
@@ -1605,15 +1557,9 @@ size_t ey_generic_mh_tril_lds(const ey_plan* pl) {
 int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                        const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                        uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  if (pl->m.P > RAM_MAX_P)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "MH with a factor: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
-                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
-  if (ey_generic_mh_tril_lds(pl) > 160 * 1024)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "MH with a factor: the factor and the model's evaluation image (" +
-                                    std::to_string(ey_generic_mh_tril_lds(pl)) +
-                                    " bytes) do not fit the 160 KiB LDS of a CU");
-  return EY_TINY_DISPATCH(launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, temp, C, seed, iter, chain_offset,
-                          accepted, log_rate, s, run);
+  if (int rc = tril_limits(pl, "MH with a factor", "the factor", "the factor", ey_generic_mh_tril_lds(pl))) return rc;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, temp, C, seed,
+                          iter, chain_offset, accepted, log_rate, s, run);
 }
 
 // ----------------------------------------------------------------------------------------------- MALA with a fixed factor
@@ -1671,20 +1617,13 @@ __global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* targ
   const bool ht = temp != nullptr;
   const T tc = ht ? temp[c] : T(1);
   const T eps = step_vec ? step_vec[c] : step;
-  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c);
-  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
-  const T* Lg = tril + g * (int64_t)P * P;
-  for (int j = 0; j < P; ++j)
-    for (int i = j + lane; i < P; i += WAVE) S[ram_col(j, P) + i - j] = Lg[(int64_t)i * P + j];
+  EY_CHAIN_FACTOR(Lg);
+  EY_TRIL_PACK(S, Lg);
   T t_state = target[c];
   for (int it = 0; it < run.n_iters; ++it) {  // ey_mala_tril_run: see k_mala
     const uint64_t iter = iter0 + (uint64_t)it;
     const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
-    if (!z_in) fill_normals<T>(w, rn, P);
-    else {
-      for (int i = lane; i < P; i += WAVE) w[i] = z_in[c * P + i];
-      __syncthreads();
-    }
+    EY_READ_Z(w);
     // loc = kernel_mean (mala.py:35-36); a lane without a row repeats row P - 1's loads and stores
     T loc[2], acc[2];
 #pragma unroll
@@ -1697,20 +1636,9 @@ __global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* targ
       loc[r] = th + T(0.5) * eps * gi;
       acc[r] = loc[r];
     }
-    // loc + L z, MultivariateNormal(loc, scale_tril=L).sample(): k_ram's column sweep (clamped index, the term's input
-    // selected to zero: DESIGN.md 4.4) with the running sum of a row started at its loc, so that L = sqrt(step) I makes the
-    // one multiply-add per row that k_mala makes
-    for (int j = 0; j < P; ++j) {
-      const T zj = w[j];
-      const T* col = S + ram_col(j, P) - j;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int i = lane + r * WAVE;
-        const bool on = i >= j && i < P;
-        const T s = col[on ? i : j];
-        acc[r] += (on ? s : T(0)) * zj;
-      }
-    }
+    // loc + L z, MultivariateNormal(loc, scale_tril=L).sample(): k_ram's column sweep with the running sum of a row
+    // started at its loc, so that L = sqrt(step) I makes the one multiply-add per row that k_mala makes
+    EY_TRIL_SWEEP(S, w, 2, T(1), acc);
     T d[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -1745,18 +1673,8 @@ __global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* targ
         grad[c * P + i] = gp[i];
       }
     }
-    if (run.samples) {
-      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-      for (int i = lane; i < P; i += WAVE) so[i] = acc_ ? prop[i] : l.th[i];
-    }
-    if (lane == 0) {
-      if (acc_) target[c] = tv;
-      accepted[c] = acc_ ? 1 : 0;
-      if (log_rate_o) log_rate_o[c] = log_rate;
-      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
-      if (run.accept_count && acc_) run.accept_count[c] += 1;
-    }
+    EY_RECORD_SAMPLE(true, i, acc_ ? prop[i] : l.th[i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, tv, t_state, log_rate, target, accepted, log_rate_o, run);
     __syncthreads();
   }
 }
@@ -1766,16 +1684,9 @@ static int launch_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, 
                             const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
                             const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                             void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes = ey_generic_mala_tril_lds(pl);
-  int rc;
-  if ((rc = prep(k_mala_tril<T, TINY>, bytes))) return rc;
-  hipLaunchKernelGGL((k_mala_tril<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
-                     (T*)grad, (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (T)step,
-                     (const T*)step_vec, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
-                     run ? *run : one, C);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  return launch(k_mala_tril<T, TINY>, C, 1, ey_generic_mala_tril_lds(pl), s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (T)step, (const T*)step_vec,
+                (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
 size_t ey_generic_mala_tril_lds(const ey_plan* pl) {
@@ -1787,15 +1698,9 @@ int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, con
                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
                          const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
                          void* log_rate, hipStream_t s, const EyRun* run) {
-  if (pl->m.P > RAM_MAX_P)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "MALA with a factor: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
-                                    std::to_string(RAM_MAX_P) + " parameters (the factor lives in LDS)");
-  if (ey_generic_mala_tril_lds(pl) > 160 * 1024)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "MALA with a factor: the factor and the model's evaluation image (" +
-                                    std::to_string(ey_generic_mala_tril_lds(pl)) +
-                                    " bytes) do not fit the 160 KiB LDS of a CU");
-  return EY_TINY_DISPATCH(launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C,
-                          seed, iter, chain_offset, accepted, log_rate, s, run);
+  if (int rc = tril_limits(pl, "MALA with a factor", "the factor", "the factor", ey_generic_mala_tril_lds(pl))) return rc;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step,
+                          step_vec, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
 }
 
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
@@ -1844,11 +1749,7 @@ __global__ void __launch_bounds__(WAVE) k_gibbs(EyModel m, T* theta, T* target, 
     const uint64_t iter = iter0 + (uint64_t)it;
     const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
     const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
-    if (!z_in) fill_normals<T>(zs, rn, P);
-    else {
-      for (int i = lane; i < P; i += WAVE) zs[i] = z_in[c * P + i];
-      __syncthreads();
-    }
+    EY_READ_Z(zs);
     int n_acc = 0;
     for (int s = 0; s < S; ++s) {
       const int o0 = off[s], o1 = off[s + 1];
@@ -1903,16 +1804,10 @@ template <typename T, class TINY>
 static int launch_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
                         bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                         void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes = ey_generic_gibbs_lds(pl, tb);
-  int rc;
-  if ((rc = prep(k_gibbs<T, TINY>, bytes))) return rc;
-  hipLaunchKernelGGL((k_gibbs<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target,
-                     (const T*)z, (const T*)u, (const int*)tb->d_off, (const int*)tb->d_idx, (const T*)tb->d_scale, tb->S,
-                     tb->n_idx, carry ? 1 : 0, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted,
-                     (T*)log_rate, mom_acc, run ? *run : one, C);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  return launch(k_gibbs<T, TINY>, C, 1, ey_generic_gibbs_lds(pl, tb), s, pl->m, (T*)theta, (T*)target, (const T*)z,
+                (const T*)u, (const int*)tb->d_off, (const int*)tb->d_idx, (const T*)tb->d_scale, tb->S, tb->n_idx,
+                carry ? 1 : 0, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, mom_acc,
+                run ? *run : kOneDraw, C);
 }
 
 size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb) {
@@ -1928,8 +1823,8 @@ int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* t
                                     std::to_string(ey_generic_gibbs_lds(pl, tb)) +
                                     " bytes) do not fit the 160 KiB LDS of a CU");
   if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the blocks are the nodes of an MLP; this plan has none");
-  return EY_TINY_DISPATCH_MLP(launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter, chain_offset, accepted,
-                          log_rate, mom_acc, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch_mlp, launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter,
+                          chain_offset, accepted, log_rate, mom_acc, s, run);
 }
 
 // ----------------------------------------------------------------------------------------------- adaptive Metropolis
@@ -2002,11 +1897,7 @@ __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyA
     const int64_t n = idx + 1 - am.offset;
     const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
     const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
-    if (!z_in) fill_normals<T>(zs, rn, P);  // am.py:67
-    else {
-      for (int i = lane; i < P; i += WAVE) zs[i] = z_in[c * P + i];
-      __syncthreads();
-    }
+    EY_READ_Z(zs);  // am.py:67
     branch = 0;
     if (n > am.t0) {  // :68-73: the mixture uniform is drawn only here
       const T um = umix_in ? umix_in[c] : ey_rng_uniform_at<T>(ru, 1u);
@@ -2064,18 +1955,7 @@ __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyA
     }
     if (branch == 1) {  // theta + (b L) z (:73): a column sweep, one running sum per row
       T acc[2] = {T(0), T(0)};
-      for (int j = 0; j < P; ++j) {
-        const T zj = zs[j];
-        const T* col = W + ram_col(j, P) - j;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          if (r >= R) break;  // wave-uniform: P <= 64 has no second row
-          const int i = lane + r * WAVE;
-          const bool on = i >= j && i < P;
-          const T s = col[on ? i : j];
-          acc[r] += (bT * (on ? s : T(0))) * zj;
-        }
-      }
+      EY_TRIL_SWEEP(W, zs, R, bT, acc);
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         if (r >= R) break;  // wave-uniform: P <= 64 has no second row
@@ -2103,18 +1983,8 @@ __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyA
     const T nT = (T)n, n1T = (T)(n - 1);
     for (int i = lane; i < P; i += WAVE) mean[i] = (n1T * mean[i] + cur[i]) / nT;
     __syncthreads();  // the state and the mean of every row are visible
-    if (run.samples) {
-      T* so = static_cast<T*>(run.samples) + ((int64_t)it * C + c) * P;
-      for (int i = lane; i < P; i += WAVE) so[i] = cur[i];
-    }
-    if (lane == 0) {
-      if (acc_) target[c] = tv;
-      accepted[c] = acc_ ? 1 : 0;
-      if (log_rate_o) log_rate_o[c] = log_rate;
-      if (run.targets) static_cast<T*>(run.targets)[(int64_t)it * C + c] = t_state;
-      if (run.accepted) static_cast<unsigned char*>(run.accepted)[(int64_t)it * C + c] = acc_ ? 1 : 0;
-      if (run.accept_count && acc_) run.accept_count[c] += 1;
-    }
+    EY_RECORD_SAMPLE(true, i, cur[i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, tv, t_state, log_rate, target, accepted, log_rate_o, run);
     const int rebuild = n >= am.t0 ? (nacc == 0 ? 1 : 2) : 0;
     T ti[2], mi[2];
     for (int r = 0; r < 2; ++r) {
@@ -2163,15 +2033,8 @@ template <typename T, class TINY>
 static int launch_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
                      uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
                      const EyRun* run) {
-  const EyRun one = {1, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes = ey_generic_am_lds(pl);
-  int rc;
-  if ((rc = prep(k_am<T, TINY>, bytes))) return rc;
-  hipLaunchKernelGGL((k_am<T, TINY>), dim3((unsigned)C), dim3(WAVE), bytes, s, pl->m, (T*)theta, (T*)target, am,
-                     (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : one,
-                     C);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  return launch(k_am<T, TINY>, C, 1, ey_generic_am_lds(pl), s, pl->m, (T*)theta, (T*)target, am, (const T*)temp, seed, iter,
+                chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
 size_t ey_generic_am_lds(const ey_plan* pl) {
@@ -2181,11 +2044,7 @@ size_t ey_generic_am_lds(const ey_plan* pl) {
 
 int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
                   uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  if (pl->m.P > RAM_MAX_P)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "AM: P = " + std::to_string(pl->m.P) + " exceeds the limit of " +
-                                    std::to_string(RAM_MAX_P) + " parameters (the covariance lives in LDS)");
-  if (ey_generic_am_lds(pl) > 160 * 1024)
-    EY_FAIL(EY_ERR_UNSUPPORTED, "AM: the two covariance triangles and the model's evaluation image (" +
-                                    std::to_string(ey_generic_am_lds(pl)) + " bytes) do not fit the 160 KiB LDS of a CU");
-  return EY_TINY_DISPATCH(launch_am, pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
+  if (int rc = tril_limits(pl, "AM", "the covariance", "the two covariance triangles", ey_generic_am_lds(pl))) return rc;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_am, pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted,
+                          log_rate, s, run);
 }
