@@ -20,6 +20,7 @@ EY_RECOMPUTE_INITIAL_GRAD, EY_FORCE_GENERIC, EY_GIBBS_CARRY = 1, 2, 4
 _vp, _i, _i64, _u64, _u32, _d = ct.c_void_p, ct.c_int, ct.c_int64, ct.c_uint64, ct.c_uint32, ct.c_double
 EY_OPT_F32_PRODUCTS, EY_PRODUCTS_BF16X3, EY_PRODUCTS_EXACT = 1, 0, 1
 EY_OPT_ROW_WAVES, EY_ROW_WAVES_OFF, EY_ROW_WAVES_ON, EY_ROW_WAVES_AUTO = 2, 0, 1, 2
+EY_OPT_MAX_CHUNK_CHAINS = 3
 EY_PRIOR_NORMAL, EY_PRIOR_LAPLACE, EY_PRIOR_STUDENT_T = 0, 1, 2
 EY_LIK_BCE_SUM, EY_LIK_CE_SUM, EY_LIK_GAUSS_SUM, EY_LIK_LAPLACE_SUM, EY_LIK_POISSON_SUM = 0, 1, 2, 3, 4
 

@@ -277,12 +277,19 @@ extern "C" int ey_plan_set_option(ey_plan* pl, int option, int value) {
     pl->row_waves = value;
     return EY_OK;
   }
+  if (option == EY_OPT_MAX_CHUNK_CHAINS) {
+    if (value < 0)
+      EY_FAIL(EY_ERR_INVALID, "ey_plan_set_option: EY_OPT_MAX_CHUNK_CHAINS takes 0 (the default rule) or a positive chain count");
+    pl->max_chunk_chains = value;
+    return EY_OK;
+  }
   EY_FAIL(EY_ERR_INVALID, "ey_plan_set_option: unknown option");
 }
 extern "C" int ey_plan_get_option(const ey_plan* pl, int option, int* value) {
   if (!pl || !value) EY_FAIL(EY_ERR_INVALID, "ey_plan_get_option: null argument");
   if (option == EY_OPT_F32_PRODUCTS) { *value = pl->products; return EY_OK; }
   if (option == EY_OPT_ROW_WAVES) { *value = pl->row_waves; return EY_OK; }
+  if (option == EY_OPT_MAX_CHUNK_CHAINS) { *value = pl->max_chunk_chains; return EY_OK; }
   EY_FAIL(EY_ERR_INVALID, "ey_plan_get_option: unknown option");
 }
 // the fused MFMA kernel serves this plan with the batch it currently holds

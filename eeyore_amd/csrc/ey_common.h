@@ -96,6 +96,7 @@ struct ey_plan {
   int variant = 0;   // diagnostic switches (ey_plan_set_variant; bits as documented in include/eeyore_amd.h)
   int products = 0;  // EY_OPT_F32_PRODUCTS: EY_PRODUCTS_BF16X3 (0) or EY_PRODUCTS_EXACT (1)
   int row_waves = 0; // EY_OPT_ROW_WAVES: EY_ROW_WAVES_OFF (0, default), _ON (1), _AUTO (2)
+  int max_chunk_chains = 0;  // EY_OPT_MAX_CHUNK_CHAINS: 0 (default) the layerwise path's own rule, k > 0 at most k chains per chunk
   // layerwise batched-GEMM path for models whose parameters do not fit LDS (ey_large.hip): workspace it owns
   void* d_work;
   size_t work_bytes;

@@ -2510,6 +2510,7 @@ static int chunk_size(const ey_plan* pl, int64_t C) {
   int64_t cc = (int64_t)(cap / (per_chain ? per_chain : 1));
   if (cc < 1) cc = 1;
   if (cc > 32768) cc = 32768;  // gridDim.z
+  if (pl->max_chunk_chains > 0 && cc > pl->max_chunk_chains) cc = pl->max_chunk_chains;  // EY_OPT_MAX_CHUNK_CHAINS
   return (int)(cc < C ? cc : C);
 }
 

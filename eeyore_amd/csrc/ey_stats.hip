@@ -575,8 +575,10 @@ extern "C" int ey_inse_multivariate(const void* x, int64_t n, int64_t C, int64_t
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)MW_LDS_BYTES));
     // The centred chains of one launch lie in a workspace of 64 columns per iteration whatever p is: bounded (EY_MV_WORKSPACE_MB,
     // 1 GiB by default), the chains going through it in as many launches as that takes (4096 chains x 10 000 iterations would
-    // otherwise ask HIP's pool -- not torch's cache, which holds the device -- for 21 GB at once).
-    static const size_t cap = [] { const char* e = getenv("EY_MV_WORKSPACE_MB"); return (size_t)(e && atoi(e) > 0 ? atoi(e) : 1024) << 20; }();
+    // otherwise ask HIP's pool -- not torch's cache, which holds the device -- for 21 GB at once).  The cap is read at every
+    // call: the tests name their chain counts from it.
+    const char* cap_env = getenv("EY_MV_WORKSPACE_MB");
+    const size_t cap = (size_t)(cap_env && atoi(cap_env) > 0 ? atoi(cap_env) : 1024) << 20;
     const size_t per_chain = (size_t)n * MW_P * sizeof(double);
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(C, (int64_t)(cap / per_chain)));
     double* xcw = nullptr;

@@ -190,6 +190,19 @@ class Plan:
         L.check(L.lib().ey_plan_set_option(self.handle, L.EY_OPT_ROW_WAVES, ("off", "on", "auto").index(mode)),
                 "ey_plan_set_option")
 
+    @property
+    def max_chunk_chains(self):
+        """Most chains the layerwise path ('bgemm') runs in one set of launches (EY_OPT_MAX_CHUNK_CHAINS in
+        include/eeyore_amd.h); 0, the default, leaves it to the path's own rule (16 GiB of activations, 32768 chains).  A
+        positive value bounds the activation scratch by that many chains'; the results do not depend on it."""
+        v = ct.c_int()
+        L.check(L.lib().ey_plan_get_option(self.handle, L.EY_OPT_MAX_CHUNK_CHAINS, ct.byref(v)), "ey_plan_get_option")
+        return v.value
+
+    @max_chunk_chains.setter
+    def max_chunk_chains(self, k):
+        L.check(L.lib().ey_plan_set_option(self.handle, L.EY_OPT_MAX_CHUNK_CHAINS, int(k)), "ey_plan_set_option")
+
     def set_variant(self, variant):
         """Diagnostic switches of THIS plan (ey_plan_set_variant); returns the previous value."""
         return L.lib().ey_plan_set_variant(self.handle, int(variant))

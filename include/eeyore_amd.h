@@ -80,7 +80,7 @@ enum ey_dtype { EY_F32 = 0, EY_F64 = 1 }; /* model.dtype, eeyore/models/model.py
  *     relu; CE-sum on 3 logits or BCE-sum on one sigmoid output), which otherwise run on "fused16";
  *   EY_PRODUCTS_EXACT: v_mfma_f32_32x32x2_f32 (16x16x4 on "fused16"), bit for bit a k-ordered f32 fma chain.
  * The environment variable EY_F32_PRODUCTS=exact|bf16x3 sets what new plans start with. */
-enum ey_option { EY_OPT_F32_PRODUCTS = 1, EY_OPT_ROW_WAVES = 2 };
+enum ey_option { EY_OPT_F32_PRODUCTS = 1, EY_OPT_ROW_WAVES = 2, EY_OPT_MAX_CHUNK_CHAINS = 3 };
 enum ey_products { EY_PRODUCTS_BF16X3 = 0, EY_PRODUCTS_EXACT = 1 };
 /* EY_OPT_ROW_WAVES: tiny models (at most three layers, eight inputs, other widths <= 4: the reference's own test and example
  * models) on batches of 128 rows or more may give a chain up to four waves, each taking every fourth 64-row tile of an
@@ -92,6 +92,10 @@ enum ey_products { EY_PRODUCTS_BF16X3 = 0, EY_PRODUCTS_EXACT = 1 };
  * chip idle (chains <= 4 x CUs), so a chain's last bits follow the launch's chain count: BASELINE config 2 (MALA, 256
  * chains, N = 256) 7.7 -> 5.4 us per draw (tools/bench_configs.py opts in). */
 enum ey_row_waves { EY_ROW_WAVES_OFF = 0, EY_ROW_WAVES_ON = 1, EY_ROW_WAVES_AUTO = 2 };
+/* EY_OPT_MAX_CHUNK_CHAINS: the layerwise path ("bgemm") runs a call's chains in chunks, one set of launches per chunk, so
+ * that the activations of a chunk fit a scratch budget: min(16 GiB / activation bytes per chain, 32768) chains.  Value 0
+ * (default) is that rule; k > 0 bounds a chunk by k chains as well, which bounds the scratch by k chains' activations;
+ * negative values are refused.  A workgroup of this path sees one chain, so a chain's bits do not depend on the value. */
 
 enum ey_flags {
   EY_RECOMPUTE_INITIAL_GRAD = 1, /* HMC: re-evaluate the gradient at the start of the trajectory exactly as
@@ -430,7 +434,8 @@ int ey_inse_univariate(const void* x, int64_t n, int64_t S, int dtype, void* sig
 
 /* The reference's MULTIVARIATE initial-sequence estimator (eeyore/stats/inse_mc_cov.py:9-83, adjust=False) for C
  * chains of p <= 64 parameters at once (up to 16, with n p doubles inside 144 KiB, the chain lies in LDS; beyond that the
- * centred chains go through a workspace the call allocates and frees on the stream): x is addressed as x[i * stride_n + c * stride_c + j] (elements; a chain buffer
+ * centred chains go through a workspace the call allocates and frees on the stream -- at most EY_MV_WORKSPACE_MB from the
+ * environment, read at every call, 1024 by default, the chains taking as many launches as that needs): x is addressed as x[i * stride_n + c * stride_c + j] (elements; a chain buffer
  * [iterations, C, P] has stride_n = C*P, stride_c = P; [C, n, p] has stride_n = p, stride_c = n*p).  sig [C,p,p]
  * double: the estimate (NaN where the reference raises 'Not enough samples'); cov [C,p,p] double or NULL: the unbiased
  * sample covariance (eeyore/stats/cov.py:5-15); mean [C,p] double or NULL; num_pairs [C] int32 or NULL.  With these,

@@ -70,6 +70,17 @@ def uniform(C, seed, it, chain_offset=0, dtype=np.float32):
     return ((o0.astype(np.uint64) << np.uint64(21)) | (o1 >> np.uint32(11)).astype(np.uint64)).astype(np.float64) * 2.0 ** -53
 
 
+def uniform_blocks(chains, S, seed, it, dtype=np.float32):
+    """out[i, s] of ey_philox_uniform_blocks for the chain indices `chains` (chain_offset included): the uniform stream
+    at block word s (s = 0 is `uniform`'s variate)."""
+    chain = np.asarray(chains, dtype=np.uint64)[:, None]
+    k0, k1, c1, c2, c3 = _key_counter(seed, chain, it, STREAM_UNIFORM)
+    o0, o1, _, _ = philox4x32_10(np.arange(S, dtype=np.uint32)[None, :], c1, c2, c3, k0, k1)
+    if dtype == np.float32:
+        return (o0 >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return ((o0.astype(np.uint64) << np.uint64(21)) | (o1 >> np.uint32(11)).astype(np.uint64)).astype(np.float64) * 2.0 ** -53
+
+
 def normal(C, P, seed, it, chain_offset=0, dtype=np.float32):
     """out[c, i] of ey_philox_normal (what p0 / z = NULL draws in the step kernels)."""
     chain = (np.arange(C, dtype=np.uint64) + np.uint64(chain_offset))[:, None]

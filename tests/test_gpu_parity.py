@@ -1961,10 +1961,12 @@ def test_inse_univariate_kernel_on_the_reference_chains():
 
 
 @pytest.mark.parametrize("n,S,tag", [(2, 5, "f64"), (3, 33, "f64"), (64, 100, "f32"), (257, 1000, "f64"),
-                                     (1000, 4 * 1315, "f32"), (2500, 37, "f64"), (5000, 19, "f32"), (20000, 3, "f32")])
+                                     (1000, 4 * 1315, "f32"), (2500, 37, "f64"), (5000, 19, "f32"), (20000, 3, "f32"),
+                                     (5000, 3, "f64")])
 def test_inse_univariate_kernel_vs_oracle(n, S, tag):
-    """Series lengths that take each staging shape (16, 4 and 1 series per workgroup), ragged series counts, constant
-    series (the reference raises 'Not enough samples': NaN here) and strongly correlated ones."""
+    """Series lengths that take each staging shape (16, 4 and 1 series per workgroup; one per workgroup from n > 4608 in
+    f64, n > 9216 in f32), ragged series counts, constant series (the reference raises 'Not enough samples': NaN here) and
+    strongly correlated ones."""
     from eeyore_amd.stats import batched
     from oracle import diagnostics_oracle as do
     npdt, dt = (np.float64, torch.float64) if tag == "f64" else (np.float32, torch.float32)
@@ -1991,6 +1993,18 @@ def test_inse_univariate_kernel_vs_oracle(n, S, tag):
             assert pairs[j] == used
         np.testing.assert_allclose(var[j], do.sample_var(col.astype(np.float64)), rtol=tol)
     assert np.isnan(sig2[S // 2])
+
+
+def test_inse_univariate_refuses_a_series_beyond_lds():
+    """One series per workgroup is the last staging shape: 144 KiB of LDS hold 18432 f64 or 36864 f32 iterations, one more
+    is refused (and nothing is written)."""
+    from eeyore_amd.stats import batched
+    for dt, n in ((torch.float64, 18432), (torch.float32, 36864)):
+        x = _t(np.random.default_rng(n).standard_normal((n + 1, 2)), dt)
+        with pytest.raises(RuntimeError, match="does not fit LDS"):
+            batched.inse_univariate(x)
+        r = batched.inse_univariate(x[:n].contiguous())   # the limit itself is served
+        assert torch.isfinite(r["sig2"]).all() and (r["pairs"] > 0).all()
 
 
 def test_chain_buffer_ess_after_a_short_run():
@@ -2582,11 +2596,30 @@ def test_chain_buffer_offloads_asynchronously_and_writes_reference_files(tmp_pat
 def test_batched_gemm_vs_torch_bmm(M, N, K, kfast, act, products):
     """The batched f32 product of the config-5 path (ey_large.hip: DMA-staged 128 x 128 kernel, the narrow kernels and the
     N-remainder split) against torch.bmm in f64 plus the activation, both operand orders, ragged M / N."""
+    _batched_gemm_vs_torch_bmm(M, N, K, kfast, act, products, 5)
+
+
+# Block counts around the multiples of eight: xcd_block() (ey_large.hip) remaps the first `total & ~7` dispatch indices,
+# logical = (id % 8) * (total / 8) + id / 8, and leaves the rest where they are; a map that is no bijection leaves a tile
+# of C at its NaN fill.  Grids from bgemm_one's tile rule, (gx, gy, gz) = (block columns, block rows, batch):
+#   128 x 128 x 64: neither side <= 32, one 128 x 128 tile            -> (1, 1, batch), total = batch
+#   64 x 20 x 40:   N <= 32, the 128 x 32 tile k_bgemm<1, 1, 4, 1>     -> (1, 1, batch), total = batch
+#   256 x 128 x 64: two block rows                                    -> (1, 2, batch), total = 2 batch (8, 16 and 18 = 16 + 2)
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K,kfast,batches", [(128, 128, 64, True, (7, 8, 9, 15, 16, 17)),
+                                                 (64, 20, 40, True, (7, 8, 9, 15, 16, 17)),
+                                                 (256, 128, 64, False, (4, 8, 9))])
+@pytest.mark.parametrize("products", ["bf16x3", "exact"])
+def test_batched_gemm_block_counts_around_multiples_of_eight(M, N, K, kfast, batches, products):
+    for batch in batches:
+        _batched_gemm_vs_torch_bmm(M, N, K, kfast, 1, products, batch)
+
+
+def _batched_gemm_vs_torch_bmm(M, N, K, kfast, act, products, batch):
     import ctypes as ct
     from eeyore_amd import _lib as L
     torch.manual_seed(M + N + K)
     dev = torch.device("cuda", 0)
-    batch = 5
     bias = torch.randn(batch, N, device=dev)
     if kfast:   # A [M, K], B stored [N, K]: k contiguous in both
         A = torch.randn(batch, M, K, device=dev)

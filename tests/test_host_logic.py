@@ -56,6 +56,39 @@ def test_argument_errors_without_gpu():
     assert lib.ey_plan_destroy(None) == 0
 
 
+def test_max_chunk_chains_option_surface():
+    """EY_OPT_MAX_CHUNK_CHAINS: the header's number is the binding's, a null plan is refused with a message, and -- where
+    ey_plan_create finds a device; a plan cannot exist without one (tests/test_chain_chunks.py::test_option_surface is the
+    same on the GPU through Plan.max_chunk_chains) -- the default is 0, values round-trip and negative ones are refused."""
+    hdr = open(os.path.join(ROOT, "include", "eeyore_amd.h")).read()
+    options = dict(re.findall(r"(EY_OPT_[A-Z0-9_]+) = (\d+)", re.search(r"enum ey_option \{([^}]*)\}", hdr).group(1)))
+    assert {k: int(v) for k, v in options.items()} == {
+        "EY_OPT_F32_PRODUCTS": L.EY_OPT_F32_PRODUCTS, "EY_OPT_ROW_WAVES": L.EY_OPT_ROW_WAVES,
+        "EY_OPT_MAX_CHUNK_CHAINS": L.EY_OPT_MAX_CHUNK_CHAINS}
+    from eeyore_amd.plan import Plan
+    assert isinstance(Plan.max_chunk_chains, property) and Plan.max_chunk_chains.fset is not None
+    lib = L.lib()
+    v = ct.c_int(-7)
+    assert lib.ey_plan_set_option(None, L.EY_OPT_MAX_CHUNK_CHAINS, 3) == -1 and b"null plan" in lib.ey_last_error()
+    assert lib.ey_plan_get_option(None, L.EY_OPT_MAX_CHUNK_CHAINS, ct.byref(v)) == -1 and v.value == -7
+    h = ct.c_void_p()
+    rc = lib.ey_plan_create(ct.byref(h), 2, (ct.c_int * 3)(4, 3, 3), (ct.c_int * 2)(1, 1), (ct.c_int * 2)(1, 0), 1, 1, 0)
+    if rc != 0:
+        assert rc in (-1, -3) and len(lib.ey_last_error()) > 0   # no such device / HIP runtime error, with a message
+        return
+    try:
+        assert lib.ey_plan_get_option(h, L.EY_OPT_MAX_CHUNK_CHAINS, ct.byref(v)) == 0 and v.value == 0
+        for k in (1, 3, 32768, 2 ** 31 - 1, 0, 5):
+            assert lib.ey_plan_set_option(h, L.EY_OPT_MAX_CHUNK_CHAINS, k) == 0
+            assert lib.ey_plan_get_option(h, L.EY_OPT_MAX_CHUNK_CHAINS, ct.byref(v)) == 0 and v.value == k
+        for bad in (-1, -2 ** 31):
+            assert lib.ey_plan_set_option(h, L.EY_OPT_MAX_CHUNK_CHAINS, bad) == -1
+            assert b"EY_OPT_MAX_CHUNK_CHAINS" in lib.ey_last_error()
+            assert lib.ey_plan_get_option(h, L.EY_OPT_MAX_CHUNK_CHAINS, ct.byref(v)) == 0 and v.value == 5
+    finally:
+        assert lib.ey_plan_destroy(h) == 0
+
+
 # ------------------------------------------------------------------------------------------------ model surface
 def test_hyperparameters_validation():
     with pytest.raises(ValueError):

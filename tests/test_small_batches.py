@@ -309,13 +309,10 @@ def _equal_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-@pytest.mark.parametrize("fam,dims,acts,bias,lik,tag,kern,opts,C,N", CASES)
-def test_small_batch_vs_oracle(fam, dims, acts, bias, lik, tag, kern, opts, C, N):
-    ca = Case(fam, dims, acts, bias, lik, tag, kern, opts, C, N)
-    pl = ca.plan()
-    r = _sequence(pl, ca)
-    f64, rt, at, P = ca.f64, ca.rt, ca.at, ca.P
-    info = (fam, dims, tag, C, N)
+def _compare(pl, ca, r):
+    """The results of `_sequence` on `pl` against the oracle, chain by chain (tests/test_chain_chunks.py uses it too)."""
+    f64, rt, at, C = ca.f64, ca.rt, ca.at, ca.C
+    info = (ca.fam, ca.dims, "f64" if f64 else "f32", C, ca.N)
 
     # 1. hmc_step: decisions outside the margin and the states they lead to
     th, t, g, acc_k, _, _, _ = r["hmc"]
@@ -396,6 +393,15 @@ def test_small_batch_vs_oracle(fam, dims, acts, bias, lik, tag, kern, opts, C, N
         _, _, lk, _ = ca.co.log_target_grad(ca.th0[c].astype(np.float64), want_grad=False)
         np.testing.assert_allclose(rows[c].sum(), lk, rtol=1e-9 if f64 else 2e-4, atol=1e-9 if f64 else 2e-3,
                                    err_msg=str(info))
+
+
+@pytest.mark.parametrize("fam,dims,acts,bias,lik,tag,kern,opts,C,N", CASES)
+def test_small_batch_vs_oracle(fam, dims, acts, bias, lik, tag, kern, opts, C, N):
+    ca = Case(fam, dims, acts, bias, lik, tag, kern, opts, C, N)
+    pl = ca.plan()
+    r = _sequence(pl, ca)
+    _compare(pl, ca, r)
+    info = (fam, dims, tag, C, N)
 
     # independence from workspace history: a second plan, each call behind a GROW-chain call through the same entry point
     if C == 1:
