@@ -29,6 +29,8 @@ SYMBOLS = {
     "ey_last_error": (ct.c_char_p, []),
     "ey_plan_create": (_i, [ct.POINTER(_vp), _i, ct.POINTER(_i), ct.POINTER(_i), ct.POINTER(_i), _i, _i, _i]),
     "ey_plan_create_mixture": (_i, [ct.POINTER(_vp), _i64, _i, ct.POINTER(_d), ct.POINTER(_d), ct.POINTER(_d), _i, _i]),
+    "ey_plan_create_exptilt": (_i, [ct.POINTER(_vp), _i64, ct.POINTER(_d), ct.POINTER(_d), ct.POINTER(_d), ct.POINTER(_d), _i,
+                                    _i]),
     "ey_plan_destroy": (_i, [_vp]),
     "ey_plan_num_params": (_i, [_vp, ct.POINTER(_i64)]),
     "ey_plan_kernel": (ct.c_char_p, [_vp]),

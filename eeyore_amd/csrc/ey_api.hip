@@ -48,7 +48,10 @@ static void set_lik_constants(ey_plan* pl, double s) {
   m.lik_c = c;
   pl->lik_scale = s;
 }
-static bool is_mix(const ey_plan* pl) { return pl->m.kind == EY_KIND_MIX; }
+// a plan whose target is a density on theta itself (ey_plan_create_mixture, ey_plan_create_exptilt): no data, prior or network
+static bool is_mix(const ey_plan* pl) { return pl->m.kind == EY_KIND_MIX || pl->m.kind == EY_KIND_TILT; }
+// ... as the messages name it
+static std::string mix_noun(const ey_plan* pl) { return pl->m.kind == EY_KIND_MIX ? "a mixture plan" : "a distribution plan"; }
 
 extern "C" {
 
@@ -230,6 +233,98 @@ int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, con
   return EY_OK;
 }
 
+// A separable exponential-tilt target on theta itself: log p = sum_i [c_i + a_i theta_i - b_i exp(s_i theta_i)], the densities
+// of the reference's Gamma examples (theta = log x, the Jacobian in the closure) and their relatives.
+// Everything is validated on the host before the device is touched.
+int ey_plan_create_exptilt(ey_plan** out, int64_t P, const double* c, const double* a, const double* b, const double* s,
+                           int dtype, int device_id) {
+  const char* who = "ey_plan_create_exptilt";
+  if (!out) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  *out = nullptr;
+  if (!c || !a || !b || !s) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": dtype must be EY_F32 or EY_F64");
+  if (P < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": P must be >= 1");
+  if (P > EY_MIX_MAX_P)
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": P = " + std::to_string(P) + " exceeds the limit of " +
+                                    std::to_string(EY_MIX_MAX_P) + " parameters");
+  for (int64_t i = 0; i < P; ++i) {
+    const std::string at = "[" + std::to_string(i) + "]";
+    if (!std::isfinite(c[i])) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": c" + at + " is not finite");
+    if (!std::isfinite(a[i])) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a" + at + " is not finite");
+    if (!std::isfinite(b[i])) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": b" + at + " is not finite");
+    if (!std::isfinite(s[i])) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": s" + at + " is not finite");
+    if (!(b[i] > 0.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": b" + at + " is not > 0");
+    if (s[i] == 0.0) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": s" + at + " is 0");
+    if (!(a[i] / s[i] > 0.0))
+      EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a" + at + " / s" + at + " is not > 0 (the density is not proper)");
+  }
+  ey_plan* pl = new ey_plan();
+  EyModel& m = pl->m;
+  memset(&m, 0, sizeof(m));
+  m.kind = EY_KIND_TILT;
+  m.nl = 1;
+  m.dims[0] = m.dims[1] = 1;
+  for (int l = 0; l < EY_MAX_LAYERS; ++l) m.boff[l] = -1;
+  m.P = (int)P;
+  m.N = 1;
+  ey_generic_tilt_scratch(m);
+  pl->dtype = dtype;
+  pl->device = device_id;
+  pl->has_data = pl->has_prior = true;  // the tables are the data: nothing to attach
+  pl->d_x = pl->d_y = pl->d_mu = pl->d_inv_var = nullptr;
+  pl->d_labels = nullptr;
+  pl->d_xpack = nullptr;
+  pl->cap_N = 0;
+  pl->mfma32_ok = pl->mfma32_data_ok = false;
+  pl->d_work = nullptr;
+  pl->work_bytes = 0;
+  pl->n_cu = 0;
+  // the kernel that needs the most LDS: AM, two packed triangles beside the image
+  if (ey_generic_am_lds(pl) > 160 * 1024 || ey_generic_ram_lds(pl) > 160 * 1024) {
+    const size_t need = std::max(ey_generic_am_lds(pl), ey_generic_ram_lds(pl));
+    delete pl;
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": the evaluation image and AM's covariance triangles (" +
+                                    std::to_string(need) + " bytes) do not fit the 160 KiB LDS of a CU");
+  }
+  // ---- the device from here on
+  auto fail = [&](int code, const std::string& msg) {
+    (void)hipFree(pl->d_x); (void)hipFree(pl->d_y); (void)hipFree(pl->d_mu); (void)hipFree(pl->d_inv_var);
+    delete pl;
+    ey_set_error(msg);
+    return code;
+  };
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess) return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (device_id < 0 || device_id >= ndev) return fail(EY_ERR_INVALID, std::string(who) + ": no such device");
+  hipDeviceProp_t prop;
+  if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess)
+    return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  pl->n_cu = prop.multiProcessorCount;
+  pl->variant = g_ey_default_variant.load() & (32767 & ~1024);
+  pl->products = ey_default_products();
+  pl->row_waves = EY_ROW_WAVES_OFF;
+  // tables of the plan's dtype: computed in double by the caller, rounded once here
+  const size_t es = esize(pl);
+  std::vector<float> f32;
+  auto upload = [&](void** dst, const double* src) -> hipError_t {
+    hipError_t r = hipMalloc(dst, es * P);
+    if (r != hipSuccess) return r;
+    if (es == 8) return hipMemcpy(*dst, src, es * P, hipMemcpyHostToDevice);
+    f32.assign(src, src + P);
+    return hipMemcpy(*dst, f32.data(), es * P, hipMemcpyHostToDevice);
+  };
+  if ((e = upload(&pl->d_x, c)) != hipSuccess || (e = upload(&pl->d_y, a)) != hipSuccess ||
+      (e = upload(&pl->d_mu, b)) != hipSuccess || (e = upload(&pl->d_inv_var, s)) != hipSuccess)
+    return fail(EY_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  m.x = pl->d_x;
+  m.y = pl->d_y;
+  m.mu = pl->d_mu;
+  m.inv_var = pl->d_inv_var;
+  *out = pl;
+  return EY_OK;
+}
+
 int ey_plan_destroy(ey_plan* pl) {
   if (!pl) return EY_OK;
   (void)hipSetDevice(pl->device);
@@ -318,7 +413,7 @@ static bool prefer_large(const ey_plan* pl) {
   return w >= (pl->dtype == EY_F32 ? 560 : 200);
 }
 static bool use_large(const ey_plan* pl, int nvec = 3, uint32_t flags = 0) {
-  if (is_mix(pl)) return false;  // a mixture plan has one family: the generic kernels on TargetMix
+  if (is_mix(pl)) return false;  // a distribution plan has one family: the generic kernels on its target policy
   if (ey_large_needed(pl, nvec)) return true;
   if (!prior_normal(pl)) return false;  // the generic kernels or nothing (check_ready has refused what does not fit)
   if (flags & EY_FORCE_GENERIC) return false;
@@ -344,7 +439,7 @@ const char* ey_plan_kernel(const ey_plan* pl) {
 // buffers only grow, so the only synchronisation is the reallocation when a batch is larger than any before it.
 int ey_plan_set_data(ey_plan* pl, const void* x, const void* y, int64_t N, void* stream) {
   if (!pl || !x || !y) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: null argument");
-  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: a mixture plan takes no data (its tables are fixed at creation)");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: " + mix_noun(pl) + " takes no data (its tables are fixed at creation)");
   if (N < 1 || N > (1 << 24)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_data: N out of range");
   hipStream_t s = (hipStream_t)stream;
   EY_HIP(hipSetDevice(pl->device));
@@ -387,7 +482,7 @@ int ey_plan_set_data(ey_plan* pl, const void* x, const void* y, int64_t N, void*
 
 int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stream) {
   if (!pl || !mu || !sigma) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_prior: null argument");
-  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_prior: a mixture plan has no prior (the density is the target)");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_plan_set_prior: " + mix_noun(pl) + " has no prior (the density is the target)");
   hipStream_t s = (hipStream_t)stream;
   EY_HIP(hipSetDevice(pl->device));
   EyModel& m = pl->m;
@@ -450,7 +545,7 @@ int ey_plan_set_prior_family(ey_plan* pl, int family, const void* loc, const voi
     EY_FAIL(EY_ERR_INVALID, std::string(who) + ": family must be EY_PRIOR_NORMAL, EY_PRIOR_LAPLACE or EY_PRIOR_STUDENT_T");
   const bool st = family == EY_PRIOR_STUDENT_T;
   if (st && !df) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": EY_PRIOR_STUDENT_T needs df");
-  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a mixture plan has no prior (the density is the target)");
+  if (is_mix(pl)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": " + mix_noun(pl) + " has no prior (the density is the target)");
   hipStream_t s = (hipStream_t)stream;
   EY_HIP(hipSetDevice(pl->device));
   EyModel& m = pl->m;
@@ -595,7 +690,7 @@ int ey_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, v
 }
 
 int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, void* stream) {
-  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: a mixture plan has no data rows");
+  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_UNSUPPORTED, "ey_log_lik_rows: " + mix_noun(pl) + " has no data rows");
   int rc = check_ready(pl, C, "ey_log_lik_rows", 3);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
@@ -607,7 +702,7 @@ int ey_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C,
 }
 
 int ey_forward(ey_plan* pl, const void* theta, int64_t C, void* out, void* stream) {
-  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_forward: a mixture plan has no network");
+  if (pl && is_mix(pl)) EY_FAIL(EY_ERR_INVALID, "ey_forward: " + mix_noun(pl) + " has no network");
   // (not check_ready: a prior family the layerwise kernels do not serve is no obstacle, their forward products read no prior)
   if (!pl) EY_FAIL(EY_ERR_INVALID, "ey_forward: null plan");
   if (!pl->has_data) EY_FAIL(EY_ERR_STATE, "ey_forward: ey_plan_set_data has not been called");
@@ -1132,7 +1227,7 @@ static int gibbs_impl(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* 
                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                       void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
   if (pl && is_mix(pl))
-    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": Gibbs blocks are the nodes of an MLP; a mixture plan has none");
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": Gibbs blocks are the nodes of an MLP; " + mix_noun(pl) + " has none");
   int rc = check_ready(pl, C, who);
   if (rc < 0) return rc;
   if (!tb) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null block table");
@@ -1434,7 +1529,7 @@ extern "C" int ey_plan_attach_da(ey_plan* pl, void* state, void* step_vec, const
   }
   if (is_mix(pl))
     EY_FAIL(EY_ERR_UNSUPPORTED, "ey_plan_attach_da: in-kernel dual averaging needs one of the fused kernel families; "
-                                "adapt on the host for a mixture plan");
+                                "adapt on the host for " + mix_noun(pl));
   if (!step_vec || !table || n <= 0 || C <= 0)
     EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_da: state, step_vec, table, n > 0 and C > 0 are required");
   if (!(d > 0.0 && d < 1.0)) EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_da: the target acceptance must lie in (0, 1)");

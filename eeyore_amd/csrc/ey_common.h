@@ -11,6 +11,7 @@
 #define EY_VERSION 200  // 0.2.0
 #define EY_KIND_MLP 0
 #define EY_KIND_MIX 1
+#define EY_KIND_TILT 2  // sum_i [c_i + a_i theta_i - b_i exp(s_i theta_i)] on theta itself (ey_plan_create_exptilt)
 #define EY_MIX_MAX_P 128  // RAM's and AM's limit: lane i owns rows i and i + 64
 #define EY_MIX_MAX_M 16
 
@@ -45,12 +46,12 @@ struct EyModel {
   int lik;
   int P;
   int N;                // data rows; EY_KIND_MIX: the number of components M
-  int kind;             // EY_KIND_MLP, or EY_KIND_MIX: a Gaussian mixture on theta itself (ey_plan_create_mixture)
-  const void* x;        // [N, d0]; EY_KIND_MIX: mean [M, P]
-  const void* y;        // [N, dK]; EY_KIND_MIX: prec [M, P, P], row-major, symmetric
+  int kind;             // EY_KIND_MLP, or a density on theta itself: EY_KIND_MIX (ey_plan_create_mixture), EY_KIND_TILT (_exptilt)
+  const void* x;        // [N, d0]; EY_KIND_MIX: mean [M, P]; EY_KIND_TILT: c [P]
+  const void* y;        // [N, dK]; EY_KIND_MIX: prec [M, P, P], row-major, symmetric; EY_KIND_TILT: a [P]
   const int* labels;    // [N] argmax(y,1) (CE)
-  const void* mu;       // [P]; EY_KIND_MIX: c [M]
-  const void* inv_var;  // [P] 1/sigma^2; EY_PRIOR_LAPLACE: 1/b; EY_PRIOR_STUDENT_T: 1/(nu s^2)
+  const void* mu;       // [P]; EY_KIND_MIX: c [M]; EY_KIND_TILT: b [P]
+  const void* inv_var;  // [P] 1/sigma^2; EY_PRIOR_LAPLACE: 1/b; EY_PRIOR_STUDENT_T: 1/(nu s^2); EY_KIND_TILT: s [P]
   double prior_const;   // sum_i (-log sigma_i - 0.5 log 2pi); the other families: the table of ey_plan_set_prior_family
   const void* prior_h;  // [P] EY_PRIOR_STUDENT_T: (nu + 1)/2; null otherwise
   int prior_kind;       // EY_PRIOR_NORMAL / _LAPLACE / _STUDENT_T: which loop the tail of eval_target runs (ey_generic.hip)
@@ -181,6 +182,7 @@ int ey_mid32_eval(ey_plan* pl, const float* theta, const float* temp, int C, flo
 int ey_generic_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                           void* target, void* grad, hipStream_t s);
 void ey_generic_mix_scratch(EyModel& m);  // hrows / dmax of an EY_KIND_MIX model: the evaluation scratch of mix_target
+void ey_generic_tilt_scratch(EyModel& m);  // ... of an EY_KIND_TILT model: none
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
 int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s);  // out [C, N, dK] (ey_forward)
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,

@@ -218,6 +218,10 @@ struct TinyFix {
 struct TargetMix {
   static constexpr bool on = false;
 };
+// ... or a separable exponential tilt on theta itself (EY_KIND_TILT, tilt_target below): the same form
+struct TargetTilt {
+  static constexpr bool on = false;
+};
 
 template <int CTRL, int ROWMASK, typename T>
 __device__ __forceinline__ T tiny_dpp(T v) {
@@ -582,12 +586,56 @@ void ey_generic_mix_scratch(EyModel& m) {
   m.dmax = 0;
 }
 
+// ------------------------------------------------------------------ exponential-tilt target (EY_KIND_TILT)
+// The reference's Gamma examples sample theta = log x with the Jacobian in the closure; that density and its
+// relatives (inverse Gamma, Weibull, Gumbel) are one separable family,
+//   log p = sum_i [ c_i + a_i theta_i - b_i exp(s_i theta_i) ],   d/dtheta_i = a_i - b_i s_i exp(s_i theta_i)
+// Tables shared by all chains in global memory: c (m.x), a (m.y), b (m.mu), s (m.inv_var), [P] each; lane i owns coordinates
+// i and i + 64 and reads consecutive addresses.  No scratch.  Nothing is clamped: an overflowing exp gives b e = +inf (b > 0),
+// hence a -inf term and value and a gradient component of -sign(s) inf -- never inf - inf, since a theta stays finite; an
+// underflowing one gives b e s = 0 and the component a exactly; a NaN coordinate gives a NaN value and component.
+template <typename T, bool GRAD>
+__device__ T tilt_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
+                         T* prior_out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const T* cc = static_cast<const T*>(m.x);
+  const T* aa = static_cast<const T*>(m.y);
+  const T* bb = static_cast<const T*>(m.mu);
+  const T* ss = static_cast<const T*>(m.inv_var);
+  (void)l;
+  __syncthreads();  // the position written by the caller is visible
+  T val = T(0);
+  EY_LANE_PASS(m.P, i, on) {
+    const T t = th[i], a = aa[i], s = ss[i];
+    const T be = bb[i] * Num<T>::exp(s * t);
+    const T term = cc[i] + a * t - be;
+    val += on ? term : T(0);
+    if (GRAD) {
+      const T g = a - be * s;
+      gr[i] = has_temp ? g * temp : g;
+    }
+  }
+  val = wave_sum(val);
+  if (has_temp) val *= temp;
+  if (lik_out) *lik_out = val;
+  if (prior_out) *prior_out = T(0);
+  __syncthreads();
+  return val;
+}
+// ... which has no scratch: no activation rows, no delta ping-pong
+void ey_generic_tilt_scratch(EyModel& m) {
+  m.hrows = 0;
+  m.dmax = 0;
+}
+
 template <typename T, bool GRAD, class TINY = TinyOff>
 __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
                          T* prior_out, T* row_out = nullptr, const RowWaves rw = RowWaves{0, 1, nullptr},
                          T* fwd_out = nullptr) {
   if constexpr (std::is_same<TINY, TargetMix>::value)
     return mix_target<T, GRAD>(m, l, th, gr, has_temp, temp, lik_out, prior_out);
+  if constexpr (std::is_same<TINY, TargetTilt>::value)
+    return tilt_target<T, GRAD>(m, l, th, gr, has_temp, temp, lik_out, prior_out);
   const int lane = threadIdx.x & (WAVE - 1);
   const T* x = static_cast<const T*>(m.x);
   const T* y = static_cast<const T*>(m.y);
@@ -1137,10 +1185,12 @@ static int tiny_dispatch_mlp(const ey_plan* pl, F f) {
     default: return f(TinyOff{});
   }
 }
-// ... and TargetMix for a mixture plan, in every kernel but k_gibbs (the reference's Gibbs needs MLP node blocks)
+// ... and TargetMix for a mixture plan, TargetTilt for an exponential-tilt plan, in every kernel but k_gibbs (the reference's
+// Gibbs needs MLP node blocks)
 template <typename F>
 static int tiny_dispatch(const ey_plan* pl, F f) {
   if (pl->m.kind == EY_KIND_MIX) return f(TargetMix{});
+  if (pl->m.kind == EY_KIND_TILT) return f(TargetTilt{});
   return tiny_dispatch_mlp(pl, f);
 }
 // fn<T, policy>(...) for the plan's dtype and the policy `dispatch` (tiny_dispatch or tiny_dispatch_mlp) picks

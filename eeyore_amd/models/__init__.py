@@ -5,4 +5,5 @@ from .logistic_regression import LogisticRegression
 from . import logistic_regression
 from .distribution_model import DistributionModel
 from .targets import NormalMixture, MultivariateNormal
+from .targets import ExponentialTilt, LogGamma, LogInverseGamma, LogWeibull, Gumbel
 from . import targets

@@ -2,22 +2,24 @@ import torch
 import torch.nn as nn
 
 from .base import LogTargetModel
-from .targets import NormalMixture
+from .targets import ExponentialTilt, NormalMixture
 from eeyore_amd.plan import Plan
 
 
 class DistributionModel(LogTargetModel):
     """A plain density on theta with the reference's constructor, ``theta`` parameter and ``summary``
     (eeyore/models/distribution_model.py:6-28).  ``log_pdf`` must be one of ``eeyore_amd.models.targets``
-    (``NormalMixture``, ``MultivariateNormal``): an arbitrary closure has no HIP kernel.  ``log_target`` and
+    (``NormalMixture``, ``MultivariateNormal``, or an ``ExponentialTilt`` such as ``LogGamma``): an arbitrary closure has no
+    HIP kernel.  ``log_target`` and
     ``upto_grad_log_target`` are one call into the library each, for one chain (theta [P]) or C chains ([C, P]); the data
     batch is ignored, as the reference's distribution closures ignore it."""
 
     def __init__(self, log_pdf, num_params, temperature=None, dtype=torch.float64, device='cpu', requires_grad=True):
         super().__init__(temperature=temperature, dtype=dtype, device=device)
-        if not isinstance(log_pdf, NormalMixture):
-            raise ValueError("log_pdf must be one of eeyore_amd.models.targets (NormalMixture, MultivariateNormal): the "
-                             "kernels implement Gaussian mixtures; an arbitrary Python closure cannot be a HIP kernel")
+        if not isinstance(log_pdf, (NormalMixture, ExponentialTilt)):
+            raise ValueError("log_pdf must be one of eeyore_amd.models.targets (NormalMixture, MultivariateNormal, or an "
+                             "ExponentialTilt such as LogGamma): the kernels implement Gaussian mixtures and separable "
+                             "exponential tilts; an arbitrary Python closure cannot be a HIP kernel")
         if int(num_params) != log_pdf.P:
             raise ValueError(f"num_params = {num_params}, but the target is a density on R^{log_pdf.P}")
         self.log_pdf = log_pdf
@@ -33,11 +35,14 @@ class DistributionModel(LogTargetModel):
         print("-" * 80)
 
     def _plan(self, x=None, y=None):
-        """This model's C-ABI plan (``Plan.mixture``); the batch is ignored."""
+        """This model's C-ABI plan (``Plan.mixture`` or ``Plan.exp_tilt``); the batch is ignored."""
         plan = self._hip_plan
         if plan is None:
             t = self.log_pdf
-            plan = Plan.mixture(t.c, t.means, t.prec, self.dtype, self.device)
+            if isinstance(t, ExponentialTilt):
+                plan = Plan.exp_tilt(t.c, t.a, t.b, t.s, self.dtype, self.device)
+            else:
+                plan = Plan.mixture(t.c, t.means, t.prec, self.dtype, self.device)
             object.__setattr__(self, "_hip_plan", plan)
         return plan
 

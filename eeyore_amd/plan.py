@@ -145,6 +145,42 @@ class Plan:
         self._da_refs = None
         return self
 
+    @classmethod
+    def exp_tilt(cls, c, a, b, s, dtype, device):
+        """The plan of a separable exponential-tilt target on theta itself (ey_plan_create_exptilt):
+        log p = sum_i [c_i + a_i theta_i - b_i exp(s_i theta_i)].  ``c``, ``a``, ``b``, ``s`` [P] are host arrays of doubles,
+        validated by the library before anything touches the device.  Data and prior are "set" from birth; ``kernel`` is
+        'dist'."""
+        import numpy as np
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(
+                f"eeyore_amd: the hot path runs on an MI355X through the HIP library; device '{device}' is not a ROCm "
+                "device and there is no CPU fallback")
+        if dtype not in _DT:
+            raise ValueError(f"unsupported dtype {dtype}")
+        c, a, b, s = (np.ascontiguousarray(t, dtype=np.float64) for t in (c, a, b, s))
+        if c.ndim != 1 or a.shape != c.shape or b.shape != c.shape or s.shape != c.shape:
+            raise ValueError(f"expected c, a, b and s of one shape [P], got {c.shape}, {a.shape}, {b.shape}, {s.shape}")
+        self = cls.__new__(cls)
+        self.dtype = dtype
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        self.dims = None
+        self.handle = ct.c_void_p()
+        dp = ct.POINTER(ct.c_double)
+        L.check(L.lib().ey_plan_create_exptilt(ct.byref(self.handle), c.shape[0], c.ctypes.data_as(dp), a.ctypes.data_as(dp),
+                                               b.ctypes.data_as(dp), s.ctypes.data_as(dp), _DT[dtype], idx),
+                "ey_plan_create_exptilt")
+        P = ct.c_int64()
+        L.check(L.lib().ey_plan_num_params(self.handle, ct.byref(P)), "ey_plan_num_params")
+        self.P = P.value
+        self._data_key, self._data_ref = None, (None, None)
+        self._prior_key = None
+        self._moments = None
+        self._da_refs = None
+        return self
+
     def __del__(self):
         try:
             if getattr(self, "handle", None) and self.handle.value:

@@ -126,6 +126,19 @@ int ey_plan_create(ey_plan** out, int n_layers, const int* dims, const int* bias
  * the variant switches are accepted and change nothing. */
 int ey_plan_create_mixture(ey_plan** out, int64_t P, int M, const double* c, const double* mean, const double* prec,
                            int dtype, int device_id);
+/* The same for the closures of the reference's Gamma examples and their relatives: theta = log x with the Jacobian in the
+ * closure (Gamma, inverse Gamma, Weibull) or a Gumbel density on theta itself -- one separable family on theta in R^P,
+ *   log p(theta) = sum_i [ c[i] + a[i] theta_i - b[i] exp(s[i] theta_i) ],   d/dtheta_i = a[i] - b[i] s[i] exp(s[i] theta_i)
+ * (Gamma(shape k, scale t): a = k, b = 1/t, s = 1, c = -lgamma(k) - k log t, or 0 for the unnormalised density).  c, a, b, s
+ * [P] are HOST arrays of doubles, read during the call only and rounded once to the plan's dtype.  Validated before anything
+ * touches the device, *out null on failure -- EY_ERR_INVALID: a null argument, P < 1, a non-finite entry, b[i] <= 0,
+ * s[i] == 0 or a[i] / s[i] <= 0 (the density would not be proper; the message names i); EY_ERR_UNSUPPORTED: P > 128.
+ * Nothing is clamped: where exp(s[i] theta_i) overflows the value is -inf and the gradient component -sign(s[i]) inf (a
+ * sampler rejects such a proposal), where it underflows the component is a[i] exactly, a NaN coordinate gives a NaN value.
+ * The plan serves and refuses the calls a plan of ey_plan_create_mixture does (its messages say "a distribution plan") and
+ * ey_plan_kernel says "dist". */
+int ey_plan_create_exptilt(ey_plan** out, int64_t P, const double* c, const double* a, const double* b, const double* s,
+                           int dtype, int device_id);
 int ey_plan_destroy(ey_plan* plan);
 /* Model.num_params (eeyore/models/model.py:34-36) */
 int ey_plan_num_params(const ey_plan* plan, int64_t* P);
