@@ -232,12 +232,8 @@ def other_case(sampler, family, seed=0, C=11, steps=5):
     prior with distinct tables, and what the f64 restatements (ram / am / gibbs / mh_mvn / mala_mvn _restatement with this
     module's target) make of them: per step the states [C, P], targets [C], decisions and margins |log u - log rate|
     (Gibbs: per sub-step).  Needs no GPU."""
-    from tests.am_restatement import am_draw
-    from tests.gibbs_restatement import gibbs_draw
+    from tests import cross_restatement as cr  # (it imports this module: the loop over steps and chains lives there)
     from tests.helpers import load
-    from tests.mala_mvn_restatement import mala_mvn_draw
-    from tests.mh_mvn_restatement import mh_mvn_draw
-    from tests.ram_restatement import ram_draw
     ds = load("datasets.npz")
     x, y = ds["iris_x"], ds["iris_y"]
     P = 27
@@ -251,36 +247,4 @@ def other_case(sampler, family, seed=0, C=11, steps=5):
              u=rng.random((steps, C, S) if sampler == "gibbs" else (steps, C)), u_mix=rng.random((steps, C)))
     if sampler in ("mh_tril", "mala_tril"):
         d["L"] = dense_lower(P, par["scale"], 50 + seed)
-    th = d["th0"].copy()
-    start = [tgt.value_and_grad(t) for t in th]
-    tv, gr = np.array([s[0] for s in start]), np.array([s[1] for s in start])
-    chol = np.stack([par["chol0"] * np.eye(P)] * C) if sampler == "ram" else None
-    am = [dict(mean=np.zeros(P), cov_sum=np.zeros((P, P)), cov=par["cov0"] * np.eye(P), num_accepted=0) for _ in range(C)] \
-        if sampler == "am" else None
-    out = dict(theta=[], target=[], accepted=[], margin=[], branch=[])
-    for it in range(steps):
-        acc, margin, branch = [], [], []
-        for c in range(C):
-            z, u = d["z"][it, c], d["u"][it, c]
-            if sampler == "ram":
-                th[c], tv[c], chol[c], a, lr = ram_draw(tgt.log_target, th[c], tv[c], chol[c], z, u, it + 1, par["a"], par["g"])
-            elif sampler == "am":
-                w = am_draw(tgt.log_target, th[c], tv[c], am[c]["mean"], am[c]["cov_sum"], am[c]["cov"], am[c]["num_accepted"],
-                            par["cov0"] * np.eye(P), z, d["u_mix"][it, c], u, it, 0, par["l"], par["b"], par["c"], par["t0"],
-                            par["eps"])
-                th[c], tv[c], a, lr = w["theta"], w["target"], w["accepted"], w["log_rate"]
-                am[c] = {k: w[k] for k in ("mean", "cov_sum", "cov", "num_accepted")}
-                branch.append(w["branch"])
-            elif sampler == "gibbs":
-                th[c], tv[c], a, lr, mg_ = gibbs_draw(tgt.log_target, th[c], tv[c], OTHER_BLOCKS, [par["scale"]] * S, z, u)
-                acc.append(a); margin.append(mg_)
-                continue
-            elif sampler == "mh_tril":
-                th[c], tv[c], a, lr = mh_mvn_draw(tgt.log_target, th[c], tv[c], d["L"], z, u)
-            else:
-                th[c], tv[c], gr[c], a, lr = mala_mvn_draw(tgt.value_and_grad, th[c], tv[c], gr[c], d["L"], z, u, par["step"])
-            acc.append(int(a)); margin.append(abs(np.log(u) - lr))
-        out["theta"].append(th.copy()); out["target"].append(tv.copy())
-        out["accepted"].append(np.array(acc)); out["margin"].append(np.array(margin)); out["branch"].append(np.array(branch))
-    d.update({k: np.array(v) for k, v in out.items()})
-    return d
+    return cr.run_case(sampler, tgt, par, d, blocks=OTHER_BLOCKS)

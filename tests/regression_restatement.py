@@ -139,9 +139,7 @@ def sampler_case(sampler, loss="gauss", scale=0.5, seed=0, C=11, steps=5, N=40):
     """The inputs of ``steps`` draws of C chains of one of SAMPLERS on MLP(2-3-1) (tanh, identity) under a regression
     likelihood, and what the f64 restatements make of them: per step the states [C, P], targets [C], decisions and margins
     |log u - log rate| (Gibbs: per sub-step).  Needs no GPU."""
-    from tests.am_restatement import am_draw
-    from tests.gibbs_restatement import gibbs_draw
-    from tests.ram_restatement import ram_draw
+    from tests import cross_restatement as cr  # (it imports this module: the loop over steps and chains lives there)
     x, y = synthetic(S_DIMS, loss, N, seed=20 + seed)
     tgt = Target(S_DIMS, S_ACTS, loss, x, y, scale=scale, sigma=2.0)
     P = tgt.P
@@ -151,42 +149,7 @@ def sampler_case(sampler, loss="gauss", scale=0.5, seed=0, C=11, steps=5, N=40):
     d = dict(x=x, y=y, par=par, target=tgt, lik=CODE[loss], lik_scale=scale, sigma=2.0,
              th0=0.3 * rng.standard_normal((C, P)), z=rng.standard_normal((steps, C, P)),
              u=rng.random((steps, C, S) if sampler == "gibbs" else (steps, C)), u_mix=rng.random((steps, C)))
-    th = d["th0"].copy()
-    start = [tgt.value_and_grad(t) for t in th]
-    tv, gr = np.array([s[0] for s in start]), np.array([s[1] for s in start])
-    chol = np.stack([par["chol0"] * np.eye(P)] * C) if sampler == "ram" else None
-    am = [dict(mean=np.zeros(P), cov_sum=np.zeros((P, P)), cov=par["cov0"] * np.eye(P), num_accepted=0) for _ in range(C)] \
-        if sampler == "am" else None
-    out = dict(theta=[], target=[], accepted=[], margin=[], branch=[])
-    for it in range(steps):
-        acc, margin, branch = [], [], []
-        for c in range(C):
-            z, u = d["z"][it, c], d["u"][it, c]
-            if sampler == "hmc":
-                th[c], tv[c], gr[c], a, lr = hmc_draw(tgt.value_and_grad, th[c], tv[c], gr[c], z, u, par["step"], par["L"])
-                lr = min(lr, 0.0)  # the decision is u < min(exp(log rate), 1)
-            elif sampler == "mala":
-                th[c], tv[c], gr[c], a, lr = mala_draw(tgt.value_and_grad, th[c], tv[c], gr[c], z, u, par["step"])
-            elif sampler == "mh":
-                th[c], tv[c], a, lr = mh_draw(tgt.log_target, th[c], tv[c], z, u, par["scale"])
-            elif sampler == "ram":
-                th[c], tv[c], chol[c], a, lr = ram_draw(tgt.log_target, th[c], tv[c], chol[c], z, u, it + 1, par["a"], par["g"])
-            elif sampler == "am":
-                w = am_draw(tgt.log_target, th[c], tv[c], am[c]["mean"], am[c]["cov_sum"], am[c]["cov"], am[c]["num_accepted"],
-                            par["cov0"] * np.eye(P), z, d["u_mix"][it, c], u, it, 0, par["l"], par["b"], par["c"], par["t0"],
-                            par["eps"])
-                th[c], tv[c], a, lr = w["theta"], w["target"], w["accepted"], w["log_rate"]
-                am[c] = {k: w[k] for k in ("mean", "cov_sum", "cov", "num_accepted")}
-                branch.append(w["branch"])
-            else:
-                th[c], tv[c], a, lr, mg_ = gibbs_draw(tgt.log_target, th[c], tv[c], S_BLOCKS, [par["scale"]] * S, z, u)
-                acc.append(a); margin.append(mg_)
-                continue
-            acc.append(int(a)); margin.append(abs(np.log(u) - lr))
-        out["theta"].append(th.copy()); out["target"].append(tv.copy())
-        out["accepted"].append(np.array(acc)); out["margin"].append(np.array(margin)); out["branch"].append(np.array(branch))
-    d.update({k: np.array(v) for k, v in out.items()})
-    return d
+    return cr.run_case(sampler, tgt, par, d, blocks=S_BLOCKS)
 
 
 # ------------------------------------------------------------------------------------------------ the closed form

@@ -228,7 +228,7 @@ def test_fixture_replay(family):
 
 
 # ------------------------------------------------------------------------------------------------ 4. the other generic samplers
-@pytest.mark.parametrize("family", ["laplace", "studentt"])
+@pytest.mark.parametrize("family", ["laplace", "studentt", "cauchy"])
 @pytest.mark.parametrize("sampler", pr.OTHER_SAMPLERS)
 def test_the_other_generic_samplers(sampler, family):
     d = pr.other_case(sampler, family)

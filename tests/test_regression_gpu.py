@@ -80,15 +80,18 @@ def test_values_against_the_reference(key, dtype):
     np.testing.assert_allclose(_np(gr), rec["grad"], **_tol(dtype))
 
 
-# name: (dims, activations, rows, row waves): the tiny register path with compile-time extents; with run-time extents, two
-# outputs and a tanh OUTPUT activation; the LDS tile loop over two full tiles and one of 22 rows (relu hidden layer); one
-# row; the row-wave form
+# name: (dims, activations, rows, row waves, variant of Plan.set_variant): the tiny register path with compile-time extents;
+# two outputs and a tanh OUTPUT activation on one partial tile of the LDS tile loop (40 rows: below the 128 from which a
+# shape without compile-time extents is evaluated in registers); the same model forced onto the register path with
+# run-time extents (variant bit 9), one wave; the LDS tile loop over two full tiles and one of 22 rows (relu hidden layer);
+# one row; the row-wave form (the register path with run-time extents, several waves)
 GENERIC = {
-    "mlp221": ([2, 2, 1], [2, 0], 40, "off"),
-    "mlp342": ([3, 4, 2], [1, 2], 40, "off"),
-    "mlp482": ([4, 8, 2], [3, 0], 150, "off"),
-    "mlp482_one_row": ([4, 8, 2], [3, 0], 1, "off"),
-    "mlp231_row_waves": ([2, 3, 1], [2, 0], 150, "on"),
+    "mlp221": ([2, 2, 1], [2, 0], 40, "off", 0),
+    "mlp342": ([3, 4, 2], [1, 2], 40, "off", 0),
+    "mlp342_tiny": ([3, 4, 2], [1, 2], 40, "off", 512),
+    "mlp482": ([4, 8, 2], [3, 0], 150, "off", 0),
+    "mlp482_one_row": ([4, 8, 2], [3, 0], 1, "off", 0),
+    "mlp231_row_waves": ([2, 3, 1], [2, 0], 150, "on", 0),
 }
 
 
@@ -102,10 +105,11 @@ def _generic_cases():
 @pytest.mark.parametrize("loss", rr.LOSSES)
 @pytest.mark.parametrize("name,C", list(_generic_cases()))
 def test_generic_values_against_torch(name, C, loss, dtype):
-    dims, acts, N, waves = GENERIC[name]
+    dims, acts, N, waves, variant = GENERIC[name]
     x, y = rr.synthetic(dims, loss, N, seed=len(name))
     pl = _plan(dims, acts, loss, x, y, dtype, scale=SCALE[loss])
     pl.row_waves = waves
+    pl.set_variant(variant)
     assert pl.kernel == "generic"
     rng = np.random.default_rng(10 * pl.P + C)
     th = _t(0.5 * rng.standard_normal((C, pl.P)), dtype)
@@ -258,7 +262,7 @@ def test_poisson_overflow_gives_a_target_the_accept_step_rejects(name):
 
 def test_the_scale_is_validated_and_enters_the_value():
     from eeyore_amd.plan import Plan
-    dims, acts, N, _ = GENERIC["mlp221"]
+    dims, acts, N = GENERIC["mlp221"][:3]
     x, y = rr.synthetic(dims, "gauss", N)
     th = _t(0.5 * np.random.default_rng(0).standard_normal((3, 9)), F64)
     for loss in ("gauss", "laplace"):
