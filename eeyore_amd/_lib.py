@@ -77,6 +77,12 @@ SYMBOLS = {
                         _vp, _vp, _vp, _vp, _vp]),
     "ey_am_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,
                        _vp, _vp, _vp, _vp, _vp]),
+    "ey_am_softabs_step": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64,
+                                _u32, _vp, _vp, _vp, _vp, _vp]),
+    "ey_am_softabs_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_am_softabs_fits": (_i, [_vp]),
+    "ey_softabs": (_i, [_vp, _i64, _i64, _i, _d, _vp, _vp, _vp]),
     "ey_gibbs_table_create": (_i, [ct.POINTER(_vp), _i64, _i, _vp, _vp, _vp, _i, _i]),
     "ey_gibbs_table_destroy": (_i, [_vp]),
     "ey_gibbs_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),

@@ -1115,7 +1115,7 @@ int ey_mala_tril_run(ey_plan* pl, void* theta, void* target, void* grad, const v
 // AM runs on k_am (ey_generic.hip) for every model, as RAM does on k_ram
 static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
                    uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, void* stream, const EyRun* run,
-                   const char* who) {
+                   const char* who, int transform = EY_AM_RIDGE) {
   int rc = check_ready(pl, C, who);
   if (rc) return rc < 0 ? rc : EY_OK;
   EyVariantScope vs(pl);
@@ -1126,14 +1126,19 @@ static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const
   if (am.t0 < 2) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": t0 must be >= 2 (the covariance divides by n - 1)");
   if (!(am.l >= 0.0 && am.l <= 1.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the mixture weight l must lie in [0, 1]");
   if (!std::isfinite(am.b) || !std::isfinite(am.c)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": b and c must be finite");
-  if (!(std::isfinite(am.eps) && am.eps >= 0.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": eps must be finite and >= 0");
+  if (transform == EY_AM_SOFTABS) {  // am.eps carries a
+    if (!(std::isfinite(am.eps) && am.eps > 0.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a must be finite and > 0");
+  } else if (!(std::isfinite(am.eps) && am.eps >= 0.0)) {
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": eps must be finite and >= 0");
+  }
   if (am.idx < 0 || am.idx + 1 - am.offset < 1)
     EY_FAIL(EY_ERR_INVALID, std::string(who) + ": idx must be >= 0 and the adaptation index idx + 1 - offset >= 1");
   if (C == 0) return EY_OK;
   if ((rc = moments_check(pl, C, who))) return rc;
   if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
   EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_am(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, (hipStream_t)stream, run);
+  rc = ey_generic_am(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, (hipStream_t)stream, run,
+                     transform);
   return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
 }
 
@@ -1159,6 +1164,46 @@ int ey_am_run(ey_plan* pl, void* theta, void* target, void* running_mean, void* 
   const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0, idx, offset,
                    nullptr, nullptr, nullptr, nullptr, (int*)breakdowns};
   return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, nullptr, stream, &run, "ey_am_run");
+}
+
+// AM with the transform softabs(cov, a) in place of the ridge: k_am's softabs instantiation
+int ey_am_softabs_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov,
+                       void* num_accepted, const void* cov0, int cov0_per_chain, double l, double b, double c, double a,
+                       int64_t t0, int64_t idx, int64_t offset, const void* z, const void* u_mix, const void* u,
+                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                       void* accepted, void* log_rate, void* branch, void* breakdowns, void* stream) {
+  (void)flags;
+  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, a, t0, idx, offset,
+                   z, u_mix, u, (unsigned char*)branch, (int*)breakdowns};
+  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, stream, nullptr,
+                 "ey_am_softabs_step", EY_AM_SOFTABS);
+}
+
+int ey_am_softabs_run(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov,
+                      void* num_accepted, const void* cov0, int cov0_per_chain, double l, double b, double c, double a,
+                      int64_t t0, int64_t idx, int64_t offset, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                      uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec,
+                      void* accept_count, void* accepted, void* breakdowns, void* stream) {
+  (void)flags;
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, a, t0, idx, offset,
+                   nullptr, nullptr, nullptr, nullptr, (int*)breakdowns};
+  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, nullptr, stream, &run,
+                 "ey_am_softabs_run", EY_AM_SOFTABS);
+}
+
+int ey_am_softabs_fits(const ey_plan* pl) { return pl && ey_generic_am_softabs_fits(pl) ? 1 : 0; }
+
+int ey_softabs(const void* A, int64_t B, int64_t P, int dtype, double a, void* out, void* sweeps, void* stream) {
+  if (!A || !out) EY_FAIL(EY_ERR_INVALID, "ey_softabs: null argument");
+  if (dtype != EY_F32 && dtype != EY_F64) EY_FAIL(EY_ERR_INVALID, "ey_softabs: bad dtype");
+  if (B < 0 || B > 0x7fffffffLL || P < 1) EY_FAIL(EY_ERR_INVALID, "ey_softabs: B or P out of range");
+  if (!(std::isfinite(a) && a > 0.0)) EY_FAIL(EY_ERR_INVALID, "ey_softabs: a must be finite and > 0");
+  if (P > 128)
+    EY_FAIL(EY_ERR_UNSUPPORTED, "ey_softabs: P = " + std::to_string(P) + " exceeds the limit of 128 (the f64 work matrix "
+                                "of one wave lives in LDS)");
+  if (B == 0) return EY_OK;
+  return ey_generic_softabs(A, B, (int)P, dtype, a, out, sweeps, (hipStream_t)stream);
 }
 
 // ---- Gibbs: blockwise random-walk Metropolis on k_gibbs (ey_generic.hip) for every model, whatever plan.kernel says

@@ -214,6 +214,8 @@ int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, con
                          const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
                          void* log_rate, hipStream_t s, const EyRun* run = nullptr);
 
+#define EY_AM_RIDGE 0
+#define EY_AM_SOFTABS 1
 // adaptive Metropolis (k_am): the state and the settings of AM.draw beside theta and target, whatever plan.kernel says
 struct EyAm {
   void* mean;           // [C, P] running_mean, in/out
@@ -222,16 +224,19 @@ struct EyAm {
   int* num_accepted;    // [C] int32, in/out
   const void* cov0;     // [P, P] or [C, P, P]: the transformed initial covariance
   int cov0_per_chain;
-  double l, b, c, eps;
+  double l, b, c, eps;  // eps: the ridge (EY_AM_RIDGE) or softabs's a (EY_AM_SOFTABS)
   int64_t t0, idx, offset;
   const void *z, *u_mix, *u;  // recorded draws [C, P], [C], [C], or null
   unsigned char* branch;      // [C] 0 isotropic, 1 factor, 2 breakdown; or null
   int* breakdowns;            // [C] int32 (+=)
 };
-size_t ey_generic_am_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
+size_t ey_generic_am_lds(const ey_plan* pl, int transform = EY_AM_RIDGE);  // dynamic LDS of one chain's workgroup
+bool ey_generic_am_softabs_fits(const ey_plan* pl);  // P <= 128 and the softabs instantiation's LDS fits a CU
+// softabs of B dense symmetric [P, P] matrices (k_softabs), the device function k_am's softabs instantiation runs
+int ey_generic_softabs(const void* A, int64_t B, int P, int dtype, double a, void* out, void* sweeps, hipStream_t s);
 int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
                   uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
-                  const EyRun* run = nullptr);
+                  const EyRun* run = nullptr, int transform = EY_AM_RIDGE);
 
 // node-blocked Metropolis-within-Gibbs (k_gibbs): blockwise random-walk Metropolis over a table of disjoint index sets
 struct ey_gibbs_table {

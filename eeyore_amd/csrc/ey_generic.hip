@@ -1877,8 +1877,192 @@ int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* t
                           chain_offset, accepted, log_rate, mom_acc, s, run);
 }
 
+// ----------------------------------------------------------------------------------------------- softabs, one wave
+// softabs(A, a) = Q diag(f(lambda)) Q^T, f(x) = x / tanh(a x), f(0) = 1 / a (eeyore/stats/metrics.py:3-5) of a symmetric
+// [P, P] matrix, P <= 128, by one wave in LDS, in f64 whatever the matrix's dtype.  f is even, so no
+// eigenvector is accumulated: one-sided (Hestenes) Jacobi rotates the COLUMNS of a dense copy G = A until every pair is
+// orthogonal to (P + 6) 2^-53 of its norms (what rounding leaves of an inner product of two freshly rotated columns: three
+// roundings per entry of either column and P additions; a tighter test can rotate for ever); then |lambda_k| = sigma_k =
+// |g_k| and
+//   softabs(A) = I / a + sum_{sigma_k > tau} ((f(sigma_k) - 1/a) / sigma_k^2) g_k g_k^T,   tau = P 2^-52 max sigma.
+// A round of the round-robin (circle) schedule holds ceil(P / 2) <= 64 disjoint column pairs: lane <-> pair, every lane
+// walks its two columns (leading dimension P | 1, odd, so the lanes' columns start in different LDS banks).  The loops
+// run for the whole wave -- rounds, rows, and the rotation pass is taken when ANY lane rotates --; a lane without a pair,
+// or whose pair is orthogonal already, stores into its own slot of `junk`.  A sweep without a rotation ends the
+// iteration, SOFTABS_MAX_SWEEPS caps it (the result is then what the columns give).  Nothing is contracted into fused
+// multiply-adds: the kernels that inline these functions (k_am, k_softabs) compute the same bits.
+#define SOFTABS_MAX_SWEEPS 80
+struct SoftabsWork {
+  double* G;     // [P] columns of ld
+  double* coef;  // [P]
+  double* junk;  // [WAVE]
+  int ld;
+};
+__host__ __device__ static inline int softabs_ld(int P) { return P | 1; }
+__host__ __device__ static size_t softabs_work_bytes(int P) {
+  return 8 * ((size_t)softabs_ld(P) * P + ((P + 3) & ~3) + WAVE);
+}
+__device__ inline SoftabsWork softabs_carve(unsigned char* p, int P) {
+  SoftabsWork w;
+  w.ld = softabs_ld(P);
+  w.G = reinterpret_cast<double*>(p);
+  w.coef = w.G + (size_t)w.ld * P;
+  w.junk = w.coef + ((P + 3) & ~3);
+  return w;
+}
+
+// G <- the symmetric matrix whose lower triangle load(i, j), j <= i, hands out.  False when an entry is not finite.
+template <typename LD>
+__device__ inline bool softabs_fill(const SoftabsWork w, int P, int lane, LD load) {
+  bool bad = false;
+  for (int j = 0; j < P; ++j)
+    for (int i = j + lane; i < P; i += WAVE) {
+      const double v = (double)load(i, j);
+      bad = bad || !(fabs(v) <= 1.7976931348623157e308);
+      w.G[j * w.ld + i] = v;
+      w.G[i * w.ld + j] = v;
+    }
+  __syncthreads();
+  return !__any(bad ? 1 : 0);
+}
+
+// the Jacobi sweeps on G, then coef_k; returns the number of sweeps (the last one rotated nothing unless the cap ended it)
+__device__ inline int softabs_jacobi(const SoftabsWork w, int P, int lane, double a) {
+#pragma clang fp contract(off)
+  double* G = w.G;
+  const int ld = w.ld;
+  const int half = (P + 1) >> 1, m1 = 2 * half - 1;  // players 0 .. m1; player m1 = P is the bye of an odd P
+  const double tol = (double)(P + 6) * 0x1p-53;
+  int sweeps = 0;
+  bool more = P > 1;
+  while (more && sweeps < SOFTABS_MAX_SWEEPS) {
+    ++sweeps;
+    more = false;
+    for (int r = 0; r < m1; ++r) {
+      const int k = lane < half ? lane : 0;
+      int p = k == 0 ? r : (r + k) % m1;
+      int q = k == 0 ? m1 : (r + m1 - k) % m1;
+      if (p > q) {
+        const int t = p;
+        p = q;
+        q = t;
+      }
+      const bool on = lane < half && q < P;
+      const double* gp = G + (on ? p : 0) * ld;
+      const double* gq = G + (on ? q : 0) * ld;
+      double al = 0.0, be = 0.0, ga = 0.0;
+      for (int i = 0; i < P; ++i) {
+        const double x = gp[i], y = gq[i];
+        al += x * x;
+        be += y * y;
+        ga += x * y;
+      }
+      const bool rot = on && fabs(ga) > tol * (sqrt(al) * sqrt(be));
+      if (__any(rot ? 1 : 0)) {  // wave-uniform
+        more = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double cr = 1.0 / sqrt(1.0 + t * t);
+        const double c = rot ? cr : 1.0, s = rot ? cr * t : 0.0;
+        double* dp = G + (rot ? p : 0) * ld;
+        double* dq = G + (rot ? q : 0) * ld;
+        for (int i = 0; i < P; ++i) {
+          const double x = dp[i], y = dq[i];
+          *(rot ? dp + i : w.junk + lane) = c * x - s * y;
+          *(rot ? dq + i : w.junk + lane) = s * x + c * y;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // sigma_k = |g_k| (lane <-> columns lane, lane + 64), the threshold, the coefficient of g_k g_k^T
+  double sig[2], smax = 0.0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int k = lane + r * WAVE;
+    const double* g = G + (k < P ? k : 0) * ld;
+    double ss = 0.0;
+    for (int i = 0; i < P; ++i) ss += g[i] * g[i];
+    sig[r] = k < P ? sqrt(ss) : 0.0;
+    smax = fmax(smax, sig[r]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) smax = fmax(smax, __shfl_xor(smax, o, WAVE));
+  const double tau = ((double)P * 0x1p-52) * smax, ia = 1.0 / a;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int k = lane + r * WAVE;
+    const double sg = sig[r] > tau ? sig[r] : 1.0;
+    const double f = sg / tanh(a * sg);
+    const double cf = sig[r] > tau ? ((f - ia) / sg) / sg : 0.0;
+    *(k < P ? w.coef + k : w.junk + lane) = cf;
+  }
+  __syncthreads();
+  return sweeps;
+}
+
+// store(i, j, v, on) takes entry (i, j), j <= i, of I / a + sum_k coef_k g_k g_k^T (k ascending, the diagonal's 1 / a added
+// last); a lane past the column's end calls it with on = false and a valid (i, j)
+template <typename ST>
+__device__ inline void softabs_emit(const SoftabsWork w, int P, int lane, double a, ST store) {
+#pragma clang fp contract(off)
+  const double ia = 1.0 / a;
+  for (int j = 0; j < P; ++j)
+    for (int i0 = j; i0 < P; i0 += WAVE) {
+      const bool on = i0 + lane < P;
+      const int i = on ? i0 + lane : j;
+      double acc = 0.0;
+      for (int k = 0; k < P; ++k) {
+        const double* g = w.G + k * w.ld;
+        acc += (w.coef[k] * g[i]) * g[j];
+      }
+      acc += i == j ? ia : 0.0;
+      store(i, j, acc, on);
+    }
+}
+
+// ey_softabs: B dense [P, P] matrices, one wave each; the lower triangle is read, the whole symmetric matrix written.  A
+// matrix with an entry that is not finite comes back as it was (its lower triangle mirrored), sweeps = -1.
+template <typename T>
+__global__ void __launch_bounds__(WAVE) k_softabs(const T* A, T* out, int* sweeps, int P, double a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const SoftabsWork w = softabs_carve(smem, P);
+  const int lane = threadIdx.x;
+  const T* Ab = A + (int64_t)blockIdx.x * P * P;
+  T* Ob = out + (int64_t)blockIdx.x * P * P;
+  int sw = -1;
+  if (softabs_fill(w, P, lane, [&](int i, int j) { return Ab[(int64_t)i * P + j]; })) {
+    sw = softabs_jacobi(w, P, lane, a);
+    softabs_emit(w, P, lane, a, [&](int i, int j, double v, bool on) {
+      if (on) {
+        Ob[(int64_t)i * P + j] = (T)v;
+        Ob[(int64_t)j * P + i] = (T)v;
+      }
+    });
+  } else {
+    for (int j = 0; j < P; ++j)
+      for (int i = j + lane; i < P; i += WAVE) {
+        const T v = Ab[(int64_t)i * P + j];
+        Ob[(int64_t)i * P + j] = v;
+        Ob[(int64_t)j * P + i] = v;
+      }
+  }
+  if (sweeps && lane == 0) sweeps[blockIdx.x] = sw;
+}
+
+int ey_generic_softabs(const void* A, int64_t B, int P, int dtype, double a, void* out, void* sweeps, hipStream_t s) {
+  const size_t bytes = softabs_work_bytes(P);
+  if (dtype == EY_F32)
+    return launch(k_softabs<float>, B, 1, bytes, s, (const float*)A, (float*)out, (int*)sweeps, P, a);
+  return launch(k_softabs<double>, B, 1, bytes, s, (const double*)A, (double*)out, (int*)sweeps, P, a);
+}
+
 // ----------------------------------------------------------------------------------------------- adaptive Metropolis
-// AM.draw (eeyore/samplers/am.py:61-107; Haario et al. 2001) with the transform cov -> cov + eps I fused.
+// AM.draw (eeyore/samplers/am.py:61-107; Haario et al. 2001) with the transform cov -> cov + eps I fused,
+// or, in the TR = EY_AM_SOFTABS instantiation, the transform softabs(cov, a): the adaptation then writes the raw covariance
+// into the work triangle and the wave transforms it there.  That instantiation lays its LDS out as position and state,
+// the AM block, then the evaluation's scratch; the dense f64 work matrix of the section above shares the scratch's place
+// (nothing of an evaluation lives between two of them), so the launch needs the larger of the two.
 // n = idx + 1 - offset.  Proposal: theta + c z while n <= t0; afterwards one more uniform u_mix picks theta + c z
 // (u_mix < l) or theta + (b L) z with L = chol(cov).  Accept as MH does; num_accepted counts accepts of idx > 0.  Then,
 // accepted or not:  mean <- ((n - 1) mean + theta) / n,  cov_sum <- cov_sum + theta theta^T,  and from n >= t0 on
@@ -1899,16 +2083,29 @@ __host__ __device__ static size_t am_extra_bytes(int P, size_t esz) {
   return esz * (2 * packed + 2 * Ppad + WAVE);
 }
 
-template <typename T, class TINY>
+// The LDS of k_am: the MH image, then the AM block (the Ridge instantiation); or position and state, the AM block, then the
+// evaluation's scratch -- activations and deltas, dead between two evaluations -- whose place the f64 work matrix of softabs
+// shares (the softabs instantiation: the launch needs the larger of the two).
+template <typename T, int TR>
+__device__ inline Lds<T> am_carve(const EyModel& m, unsigned char* smem) {
+  Lds<T> l = carve<T>(m, smem, 2);
+  if constexpr (TR == EY_AM_SOFTABS) {
+    l.act = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(l.act) + am_extra_bytes(m.P, sizeof(T)));
+    l.dl = l.act + m.hrows * TS;
+  }
+  return l;
+}
+
+template <typename T, class TINY, int TR = EY_AM_RIDGE>
 __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyAm am, const T* temp, uint64_t seed,
                                              uint64_t iter0, uint64_t chain_offset, unsigned char* accepted,
                                              T* log_rate_o, EyRun run, int64_t C) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const Lds<T> l = carve<T>(m, smem, 2);
+  const Lds<T> l = am_carve<T, TR>(m, smem);
   const int P = m.P;
   const size_t packed = ((size_t)P * (P + 1) / 2 + 3) & ~(size_t)3;
   const int Ppad = (P + 3) & ~3;
-  T* CS = reinterpret_cast<T*>(smem + lds_bytes(m, 2, sizeof(T)));
+  T* CS = reinterpret_cast<T*>(smem + (TR == EY_AM_SOFTABS ? sizeof(T) * 2 * Ppad : lds_bytes(m, 2, sizeof(T))));
   T* W = CS + packed;
   T* mean = W + packed;
   T* zs = mean + Ppad;
@@ -2058,13 +2255,26 @@ __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyA
         if (rebuild) {
           T wv;
           if (rebuild == 1) wv = c0g[(int64_t)ii * P + j];                         // :97
-          else wv = (sv - nT * (mi[r] * mj)) / n1T + (ii == j ? epsT : T(0));  // :59, then the ridge
+          else if constexpr (TR == EY_AM_RIDGE) wv = (sv - nT * (mi[r] * mj)) / n1T + (ii == j ? epsT : T(0));  // :59, then the ridge
+          else wv = (sv - nT * (mi[r] * mj)) / n1T;  // :59 as it is: the wave transforms the triangle below
           T* dw = on ? w + i : junk + lane;
           *dw = wv;
         }
       }
     }
     __syncthreads();
+    if constexpr (TR == EY_AM_SOFTABS) {
+      // W <- softabs(W, a), a = am.eps; a covariance with an entry that is not finite stays as it is (the next
+      // factorisation reports it)
+      const SoftabsWork sw = softabs_carve(reinterpret_cast<unsigned char*>(l.act), P);
+      if (rebuild == 2 && softabs_fill(sw, P, lane, [&](int i, int j) { return W[ram_col(j, P) + i - j]; })) {
+        softabs_jacobi(sw, P, lane, am.eps);
+        softabs_emit(sw, P, lane, am.eps, [&](int i, int j, double v, bool on) {
+          *(on ? W + ram_col(j, P) + i - j : junk + lane) = (T)v;
+        });
+        __syncthreads();
+      }
+    }
   }
   for (int j = 0; j < P; ++j)
     for (int i = j + lane; i < P; i += WAVE) {
@@ -2087,14 +2297,41 @@ static int launch_am(ey_plan* pl, void* theta, void* target, const EyAm& am, con
                 chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
 }
 
-size_t ey_generic_am_lds(const ey_plan* pl) {
+template <typename T, class TINY>
+static int launch_am_softabs(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C,
+                             uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate,
+                             hipStream_t s, const EyRun* run) {
+  return launch(k_am<T, TINY, EY_AM_SOFTABS>, C, 1, ey_generic_am_lds(pl, EY_AM_SOFTABS), s, pl->m, (T*)theta, (T*)target,
+                am, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
+                run ? *run : kOneDraw, C);
+}
+
+size_t ey_generic_am_lds(const ey_plan* pl, int transform) {
   const size_t esz = pl->dtype == EY_F32 ? 4 : 8;
-  return lds_bytes(pl->m, 2, esz) + am_extra_bytes(pl->m.P, esz);
+  const size_t bytes = lds_bytes(pl->m, 2, esz) + am_extra_bytes(pl->m.P, esz);
+  if (transform != EY_AM_SOFTABS) return bytes;
+  // the f64 work matrix of softabs shares the place of the evaluation's scratch (see k_am)
+  const size_t vectors = esz * 2 * (size_t)((pl->m.P + 3) & ~3);
+  const size_t eval_scratch = lds_bytes(pl->m, 2, esz) - vectors;
+  return vectors + am_extra_bytes(pl->m.P, esz) + std::max(eval_scratch, softabs_work_bytes(pl->m.P));
 }
 
 int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
-                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run,
+                  int transform) {
+  if (transform == EY_AM_SOFTABS) {
+    if (int rc = tril_limits(pl, "AM with softabs", "the covariance",
+                             "the two covariance triangles, the f64 work matrix of softabs",
+                             ey_generic_am_lds(pl, EY_AM_SOFTABS)))
+      return rc;
+    return EY_TINY_DISPATCH(tiny_dispatch, launch_am_softabs, pl, theta, target, am, temp, C, seed, iter, chain_offset,
+                            accepted, log_rate, s, run);
+  }
   if (int rc = tril_limits(pl, "AM", "the covariance", "the two covariance triangles", ey_generic_am_lds(pl))) return rc;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_am, pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted,
                           log_rate, s, run);
+}
+
+bool ey_generic_am_softabs_fits(const ey_plan* pl) {
+  return pl->m.P <= RAM_MAX_P && ey_generic_am_lds(pl, EY_AM_SOFTABS) <= 160 * 1024;
 }

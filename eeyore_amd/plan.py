@@ -711,8 +711,9 @@ class Plan:
 
     def am_step(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, l=0.05, b=1., c=1., eps=0.,
                 t0=2, offset=0, z=None, u_mix=None, u=None, temp=None, seed=0, it=0, chain_offset=0, flags=0,
-                breakdowns=None, out=None):
-        """One AM.draw (eeyore/samplers/am.py:61-107) of every chain (ey_am_step) with the ridge cov + eps I fused:
+                breakdowns=None, out=None, softabs_a=None):
+        """One AM.draw (eeyore/samplers/am.py:61-107) of every chain (ey_am_step) with the ridge cov + eps I fused, or,
+        with ``softabs_a``, the transform softabs(cov, softabs_a) (ey_am_softabs_step; ``eps`` is then not used):
         theta [C,P], target [C], running_mean [C,P], cov_sum and cov [C,P,P] (lower triangles) and num_accepted [C] int32
         are updated in place; ``cov0`` is the transformed initial covariance, ``idx`` the counter index of the draw.
         ``breakdowns`` [C] int32 is incremented for a chain whose covariance could not be factorised."""
@@ -725,20 +726,21 @@ class Plan:
                        branch=self.empty(C, dtype=torch.uint8))
         out["breakdowns"] = breakdowns
         temp, u, u_mix = self._opt(temp, C), self._opt(u, C), self._opt(u_mix, C)
-        L.check(L.lib().ey_am_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum),
-                                   L.ptr(cov), L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c),
-                                   float(eps), int(t0), int(idx), int(offset), L.ptr(z), L.ptr(u_mix), L.ptr(u),
-                                   L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
-                                   L.ptr(out["accepted"]), L.ptr(out.get("log_rate")), L.ptr(out.get("branch")),
-                                   L.ptr(breakdowns), _stream(self.device)), "ey_am_step")
+        fn, who, par = ((L.lib().ey_am_step, "ey_am_step", eps) if softabs_a is None else
+                        (L.lib().ey_am_softabs_step, "ey_am_softabs_step", softabs_a))
+        L.check(fn(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum), L.ptr(cov),
+                   L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c), float(par), int(t0),
+                   int(idx), int(offset), L.ptr(z), L.ptr(u_mix), L.ptr(u), L.ptr(temp), C, int(seed), int(it),
+                   int(chain_offset), int(flags), L.ptr(out["accepted"]), L.ptr(out.get("log_rate")),
+                   L.ptr(out.get("branch")), L.ptr(breakdowns), _stream(self.device)), who)
         self._stepped()
         return out
 
     def am_run(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, n_iters, l=0.05, b=1., c=1.,
                eps=0., t0=2, offset=0, temp=None, seed=0, it=0, chain_offset=0, flags=0, breakdowns=None, samples=None,
-               targets=None, accepted_rec=None, accept_count=None, out=None):
-        """``n_iters`` AM iterations of every chain in one launch (ey_am_run), counter indices idx, idx + 1, ...; records
-        as in ``hmc_run``."""
+               targets=None, accepted_rec=None, accept_count=None, out=None, softabs_a=None):
+        """``n_iters`` AM iterations of every chain in one launch (ey_am_run; ey_am_softabs_run with ``softabs_a``),
+        counter indices idx, idx + 1, ...; records as in ``hmc_run``."""
         C = self._theta(theta)
         if breakdowns is None:
             breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
@@ -749,14 +751,19 @@ class Plan:
         temp = self._opt(temp, C)
         n_iters = int(n_iters)
         self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_am_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum),
-                                  L.ptr(cov), L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c),
-                                  float(eps), int(t0), int(idx), int(offset), L.ptr(temp), C, int(seed), int(it),
-                                  int(chain_offset), int(flags), n_iters, L.ptr(samples), L.ptr(targets),
-                                  L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]), L.ptr(breakdowns),
-                                  _stream(self.device)), "ey_am_run")
+        fn, who, par = ((L.lib().ey_am_run, "ey_am_run", eps) if softabs_a is None else
+                        (L.lib().ey_am_softabs_run, "ey_am_softabs_run", softabs_a))
+        L.check(fn(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum), L.ptr(cov),
+                   L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c), float(par), int(t0),
+                   int(idx), int(offset), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
+                   L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
+                   L.ptr(breakdowns), _stream(self.device)), who)
         self._stepped(n_iters)
         return out
+
+    def am_softabs_fits(self):
+        """Whether the softabs instantiation of the AM kernel has room for this plan's model (ey_am_softabs_fits)."""
+        return bool(L.lib().ey_am_softabs_fits(self.handle))
 
     def pt_swap_decide(self, ell_i, ell_j, t_i, t_j, u, dlogq=None):
         return pt_swap_decide(ell_i, ell_j, t_i, t_j, u, dlogq=dlogq)

@@ -5,4 +5,4 @@ from .metropolis_hastings import MetropolisHastings
 from .power_posterior_sampler import PowerPosteriorSampler
 from .ram import RAM
 from .gibbs import Gibbs
-from .am import AM, Ridge
+from .am import AM, Ridge, SoftAbs

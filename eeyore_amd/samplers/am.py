@@ -1,4 +1,5 @@
 import math
+import warnings
 
 import torch
 
@@ -22,6 +23,26 @@ class Ridge:
         return f"Ridge({self.eps})"
 
 
+class SoftAbs:
+    """The transform of the reference's AM examples, cov -> softabs(cov, a) (``eeyore_amd.stats.softabs``), as a small
+    callable: the running covariance of the first draws is rank deficient, softabs lifts its null space to 1 / a.  ``AM``
+    recognises it and runs the eigen-decomposition inside its kernel, in f64 whatever the model's dtype.  Called on a
+    device tensor it is ``stats.batched.softabs`` (the kernel's own function), otherwise ``stats.softabs``."""
+
+    def __init__(self, a=1000.0):
+        a = float(a)
+        if not (math.isfinite(a) and a > 0.0):
+            raise ValueError(f"SoftAbs: a must be finite and > 0, got {a}")
+        self.a = a
+
+    def __call__(self, cov):
+        from eeyore_amd import stats
+        return stats.batched.softabs(cov, self.a) if cov.is_cuda else stats.softabs(cov, self.a)
+
+    def __repr__(self):
+        return f"SoftAbs({self.a})"
+
+
 class AM(SingleChainSerialSampler):
     """Adaptive Metropolis (Haario et al. 2001; eeyore/samplers/am.py:8-107) as one ``ey_am_step`` per draw.  With
     n = counter.idx + 1 - offset: propose theta + c z while n <= t0; afterwards, with probability l, theta + c z, else
@@ -29,8 +50,10 @@ class AM(SingleChainSerialSampler):
     on, set cov <- cov0 while nothing was accepted, else transform((cov_sum - n mean mean^T) / (n - 1)).  The
     factorisation runs inside the kernel.
 
-    ``transform``: None, ``Ridge(eps)`` (fused into the kernel) or any callable on a [P, P] covariance (one launch per
-    draw, the covariance passing through the callable in torch between launches).  ``theta0`` [P] is the reference's
+    ``transform``: None, ``Ridge(eps)`` or ``SoftAbs(a)`` (both fused into the kernel) or any callable on a [P, P]
+    covariance (one launch per draw, the covariance passing through the callable in torch between launches).  A model
+    beside which the work matrix of ``SoftAbs`` does not fit in LDS takes that callable path with the same object, after
+    one warning.  ``theta0`` [P] is the reference's
     single chain (torch random draws in the reference's order: z, the mixture uniform only when n > t0, u); [C, P] runs C
     chains on the in-kernel Philox streams.  ``cov0`` is [P, P] (shared) or [C, P, P].
 
@@ -62,8 +85,9 @@ class AM(SingleChainSerialSampler):
         self._configure(model, dataloader, theta0, chain, rng, seed, chain_offset, temperature)
         self.l, self.b, self.c, self.t0 = float(l), float(b), float(c), int(t0)
         self.transform, self.on_breakdown = transform, on_breakdown
-        self._generic = transform is not None and not isinstance(transform, Ridge)
+        self._generic = transform is not None and not isinstance(transform, (Ridge, SoftAbs))
         self._eps = transform.eps if isinstance(transform, Ridge) else 0.0
+        self._softabs_a = transform.a if isinstance(transform, SoftAbs) else None
         kw = dict(dtype=model.dtype, device=model.device)
         self.cov0 = cov0.clone().detach().to(**kw) if cov0 is not None else torch.eye(P, **kw)
         self._check_cov(self.cov0)
@@ -85,11 +109,13 @@ class AM(SingleChainSerialSampler):
                              f"got {tuple(cov.shape)}")
 
     def _transformed(self, cov):
-        if cov.dim() == 2 or isinstance(self.transform, Ridge):
+        if cov.dim() == 2 or isinstance(self.transform, (Ridge, SoftAbs)):
             return self.transform(cov)
         return torch.stack([self.transform(m) for m in cov])
 
     def _can_fuse(self, verbose):
+        if self._softabs_a is not None and super()._can_fuse(verbose):
+            self._route(self.model._plan(*next(iter(self.dataloader))))
         return not self._generic and super()._can_fuse(verbose)
 
     def _evaluate_target(self, plan):
@@ -157,7 +183,16 @@ class AM(SingleChainSerialSampler):
 
     def _am_args(self):
         return dict(l=self.l, b=self.b, c=self.c, eps=self._eps, t0=self.t0, temp=self._temp(), seed=self.seed,
-                    it=self._iter, chain_offset=self.chain_offset, breakdowns=self._breakdowns)
+                    it=self._iter, chain_offset=self.chain_offset, breakdowns=self._breakdowns,
+                    softabs_a=self._softabs_a)
+
+    def _route(self, plan):
+        """A SoftAbs whose work matrix does not fit beside this plan's model: the callable path, said once."""
+        if self._softabs_a is not None and not plan.am_softabs_fits():
+            warnings.warn(f"AM: the work matrix of {self.transform!r} does not fit in LDS beside this model "
+                          f"({self.model.num_params()} parameters, {self.model.dtype}); the transform runs between "
+                          "launches, one launch per draw", RuntimeWarning, stacklevel=3)
+            self._softabs_a, self._generic = None, True
 
     def _state(self):
         return self._theta, self._target, self._mean, self._cov_sum, self._cov, self._nacc, self.cov0
@@ -195,6 +230,7 @@ class AM(SingleChainSerialSampler):
 
     def draw(self, x, y, savestate=False, offset=0):
         plan = self.model._plan(x, y)
+        self._route(plan)
         if self.counter.num_batches != 1:  # am.py:64-65
             self._evaluate_target(plan)
         idx = self._index()

@@ -242,3 +242,31 @@ def mmd_chains(samples, x2, kernel, lengths=None, lengths2=None, biased=True, la
     sq = s11 / (a * a if biased else a * (a - 1)) + s22 / (b * b if biased else b * (b - 1)) - 2 * s12 / (a * b)   # [C, k]
     out = sq if squared else torch.sqrt(sq)
     return out[:, 0] if lengths is None else out.T.contiguous()
+
+
+# -------------------------------------------------------------------------------------------------- softabs, many matrices
+SOFTABS_MAX_P = 128  # the f64 work matrix of one wave lives in LDS (csrc/ey_generic.hip)
+
+
+def softabs(mats, a=1000.0, sweeps=None):
+    """``eeyore_amd.stats.softabs`` of every matrix of a device tensor [B, P, P] (or one [P, P]) in one launch
+    (``ey_softabs``: one wave per matrix, one-sided Jacobi in f64 in LDS, P <= 128).  The lower triangles are read; the
+    result has the shape and dtype of ``mats`` and is symmetric bit for bit.  A matrix with an entry that is not finite
+    comes back as it was.  ``sweeps``: an int32 tensor [B] that receives the Jacobi sweeps of each matrix.  It is the
+    function the fused adaptive-Metropolis kernel applies to its covariance (``samplers.SoftAbs``): the same bits."""
+    if not mats.is_cuda:
+        raise RuntimeError("eeyore_amd.stats.batched: the matrices must be on the ROCm device (no CPU fallback; "
+                           "eeyore_amd.stats.softabs is the torch form)")
+    if mats.dtype not in _DT or mats.dim() not in (2, 3) or mats.shape[-1] != mats.shape[-2]:
+        raise ValueError("mats must be a float32 / float64 tensor [B, P, P] or [P, P]")
+    x = mats.contiguous()
+    P = x.shape[-1]
+    B = x.shape[0] if x.dim() == 3 else 1
+    if sweeps is not None and (sweeps.dtype != torch.int32 or tuple(sweeps.shape) != (B,) or not sweeps.is_contiguous()
+                               or sweeps.device != x.device):
+        raise ValueError(f"sweeps must be a contiguous int32 tensor [{B}] on the matrices' device")
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().ey_softabs(L.ptr(x), B, P, _DT[x.dtype], float(a), L.ptr(out), L.ptr(sweeps),
+                                   ct.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "ey_softabs")
+    return out

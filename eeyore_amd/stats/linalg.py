@@ -1,5 +1,5 @@
-"""Two small matrix helpers the diagnostics need (the reference keeps them in eeyore/linalg/): a positive-definiteness
-test and the nearest positive-definite matrix.  Host-side glue on whatever device holds the matrix; not on the hot path."""
+"""Small matrix helpers (the reference keeps them in eeyore/linalg/ and eeyore/stats/metrics.py): a positive-definiteness
+test, the nearest positive-definite matrix and the softabs map.  Host-side glue on whatever device holds the matrix; not on the hot path."""
 import torch
 
 
@@ -31,3 +31,16 @@ def nearest_pd(a):
         lowest = float(torch.linalg.eigvalsh(out)[0])
         out = out + (gap - lowest * rounds * rounds) * ident
     return out
+
+
+def softabs(hessian, a=1000.0):
+    """Q diag(f(lambda)) Q^T with f(x) = x / tanh(a x) from ``torch.linalg.eigh`` (eeyore/stats/metrics.py:3-5): the
+    eigenvalues' absolute values, smoothed near zero, so that a rank-deficient covariance becomes positive definite.
+    ``hessian`` is [P, P] or [..., P, P]; the upper triangle is read, as in the reference.  f(0) = 1 / a, the limit,
+    where the reference's 0 / tanh(0) gives NaN.  For many matrices on the device see
+    ``eeyore_amd.stats.batched.softabs``."""
+    lam, vec = torch.linalg.eigh(hessian, "U")
+    al = a * lam
+    safe = torch.where(al == 0, torch.ones_like(al), al)
+    f = torch.where(al == 0, torch.full_like(lam, 1.0 / a), lam / torch.tanh(safe))
+    return (vec * f.unsqueeze(-2)) @ vec.mT

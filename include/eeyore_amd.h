@@ -376,6 +376,34 @@ int ey_am_run(ey_plan* plan, void* theta, void* target, void* running_mean, void
               uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count,
               void* accepted, void* breakdowns, void* stream);
 
+/* ey_am_step / ey_am_run with the transform softabs(cov, a) (below) in place of the ridge, as the reference's AM examples
+ * use it: from n >= t0 on, with something accepted, cov <- softabs((cov_sum - n mean mean^T) / (n-1), a), computed inside
+ * the kernel by the chain's wave in f64 for both dtypes and rounded once.  cov0 is the TRANSFORMED initial covariance, as
+ * there.  A raw covariance with an entry that is not finite stays untransformed; the factorisation of the next draw that
+ * needs it reports the breakdown.  a must be finite and > 0 (EY_ERR_INVALID).  The f64 work matrix of softabs follows the
+ * two triangles in LDS: ey_am_softabs_fits says whether a plan's model leaves room for it (1) or not (0, and the two
+ * calls return EY_ERR_UNSUPPORTED before any launch).  Everything else as ey_am_step / ey_am_run. */
+int ey_am_softabs_step(ey_plan* plan, void* theta, void* target, void* running_mean, void* cov_sum, void* cov,
+                       void* num_accepted, const void* cov0, int cov0_per_chain, double l, double b, double c, double a,
+                       int64_t t0, int64_t idx, int64_t offset, const void* z, const void* u_mix, const void* u,
+                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                       void* accepted, void* log_rate, void* branch, void* breakdowns, void* stream);
+int ey_am_softabs_run(ey_plan* plan, void* theta, void* target, void* running_mean, void* cov_sum, void* cov,
+                      void* num_accepted, const void* cov0, int cov0_per_chain, double l, double b, double c, double a,
+                      int64_t t0, int64_t idx, int64_t offset, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                      uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec,
+                      void* accept_count, void* accepted, void* breakdowns, void* stream);
+int ey_am_softabs_fits(const ey_plan* plan);
+
+/* softabs(A, a) = Q diag(f(lambda)) Q^T with f(x) = x / tanh(a x) and f(0) = 1 / a (eeyore/stats/metrics.py:3-5, which
+ * yields NaN at an eigenvalue that is exactly zero) of B dense symmetric [P,P] matrices of `dtype`, one wave each, by
+ * one-sided Jacobi in f64; the result is rounded once to `dtype`.  Only the lower triangle of A is read; out [B,P,P]
+ * receives the whole symmetric matrix and may be A.  A matrix with an entry that is not finite comes back as it was.
+ * sweeps [B] int32 (may be NULL): the Jacobi sweeps taken (0 for P = 1, -1 for a matrix left as it was).  The same device
+ * function in the same order as in ey_am_softabs_*: the same bits.  Needs no plan; runs on the current device.
+ * a finite and > 0, P >= 1 (EY_ERR_INVALID); P <= 128 (EY_ERR_UNSUPPORTED). */
+int ey_softabs(const void* A, int64_t B, int64_t P, int dtype, double a, void* out, void* sweeps, void* stream);
+
 /* PowerPosteriorSampler.between_chain_move (eeyore/samplers/power_posterior_sampler.py:135-163) decision for C
  * chain pairs: log_rate = dlogq + (t_i - t_j) * (ell_j - ell_i) with ell the UNTEMPERED log-target; swap iff
  * log(u) < log_rate (:160).  All arrays [C] of `dtype`; dlogq may be NULL (symmetric partner choice). */
