@@ -24,6 +24,14 @@ EY_OPT_MAX_CHUNK_CHAINS = 3
 EY_PRIOR_NORMAL, EY_PRIOR_LAPLACE, EY_PRIOR_STUDENT_T = 0, 1, 2
 EY_LIK_BCE_SUM, EY_LIK_CE_SUM, EY_LIK_GAUSS_SUM, EY_LIK_LAPLACE_SUM, EY_LIK_POISSON_SUM = 0, 1, 2, 3, 4
 
+# The arguments every sampler entry point ends with.  _DRAW: temp, C, seed, iter, chain_offset, flags; a step goes on with
+# accepted, log_rate (_STEP), a run with n_iters, samples, targets, accepted_rec, accept_count, accepted (_RUN); then the
+# stream.  _AM: plan, theta, target and the state and settings of the AM entry points.
+_DRAW = [_vp, _i64, _u64, _u64, _u64, _u32]
+_STEP = _DRAW + [_vp] * 3
+_RUN = _DRAW + [_i] + [_vp] * 6
+_AM = [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64]
+
 SYMBOLS = {
     "ey_version": (_i, []),
     "ey_last_error": (ct.c_char_p, []),
@@ -43,11 +51,10 @@ SYMBOLS = {
     "ey_forward": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "ey_log_target": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ey_log_target_grad": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ey_hmc_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp,
-                         _vp, _vp]),
+    "ey_hmc_step": (_i, [_vp] * 6 + [_d, _vp, _i] + _DRAW + [_vp] * 5),
     "ey_hmc_leapfrog": (_i, [_vp, _vp, _vp, _d, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
-    "ey_mala_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
-    "ey_mh_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
+    "ey_mala_step": (_i, [_vp] * 6 + [_d, _vp] + _STEP),
+    "ey_mh_step": (_i, [_vp] * 6 + _STEP),
     "ey_pt_swap_decide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "ey_pt_ladder_create": (_i, [_vp, _vp, _i, _i, ct.POINTER(_vp)]),
     "ey_pt_ladder_destroy": (_i, [_vp]),
@@ -57,36 +64,26 @@ SYMBOLS = {
     "ey_philox_block": (_i, [ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_uint32)]),
     "ey_stats_update": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "ey_plan_attach_moments": (_i, [_vp, _vp, _vp, _vp, _i64]),
-    "ey_hmc_run": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp,
-                        _vp, _vp]),
-    "ey_mala_run": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
-                         _vp]),
-    "ey_mh_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_hmc_run": (_i, [_vp] * 4 + [_d, _vp, _i] + _RUN),
+    "ey_mala_run": (_i, [_vp] * 4 + [_d, _vp] + _RUN),
+    "ey_mh_run": (_i, [_vp] * 4 + _RUN),
     "ey_log_lik_rows": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
-    "ey_ram_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
-    "ey_ram_run": (_i, [_vp, _vp, _vp, _vp, _d, _d, _u64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
-                        _vp]),
-    "ey_mh_tril_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
-    "ey_mh_tril_run": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp,
-                            _vp]),
-    "ey_mala_tril_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp,
-                               _vp, _vp]),
-    "ey_mala_tril_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,
-                              _vp, _vp, _vp, _vp]),
-    "ey_am_step": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32,
-                        _vp, _vp, _vp, _vp, _vp]),
-    "ey_am_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp,
-                       _vp, _vp, _vp, _vp, _vp]),
-    "ey_am_softabs_step": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64,
-                                _u32, _vp, _vp, _vp, _vp, _vp]),
-    "ey_am_softabs_run": (_i, [_vp] * 8 + [_i, _d, _d, _d, _d, _i64, _i64, _i64, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp,
-                               _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_ram_step": (_i, [_vp] * 6 + [_d, _d, _u64] + _STEP),
+    "ey_ram_run": (_i, [_vp] * 4 + [_d, _d, _u64] + _RUN),
+    "ey_mh_tril_step": (_i, [_vp] * 4 + [_i64] + [_vp] * 3 + _STEP),
+    "ey_mh_tril_run": (_i, [_vp] * 4 + [_i64, _vp] + _RUN),
+    "ey_mala_tril_step": (_i, [_vp] * 5 + [_i64] + [_vp] * 3 + [_d, _vp] + _STEP),
+    "ey_mala_tril_run": (_i, [_vp] * 5 + [_i64, _vp, _d, _vp] + _RUN),
+    "ey_am_step": (_i, _AM + [_vp] * 3 + _STEP + [_vp] * 2),
+    "ey_am_run": (_i, _AM + _RUN + [_vp]),
+    "ey_am_softabs_step": (_i, _AM + [_vp] * 3 + _STEP + [_vp] * 2),
+    "ey_am_softabs_run": (_i, _AM + _RUN + [_vp]),
     "ey_am_softabs_fits": (_i, [_vp]),
     "ey_softabs": (_i, [_vp, _i64, _i64, _i, _d, _vp, _vp, _vp]),
     "ey_gibbs_table_create": (_i, [ct.POINTER(_vp), _i64, _i, _vp, _vp, _vp, _i, _i]),
     "ey_gibbs_table_destroy": (_i, [_vp]),
-    "ey_gibbs_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _vp, _vp, _vp]),
-    "ey_gibbs_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64, _u32, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_gibbs_step": (_i, [_vp] * 6 + _STEP),
+    "ey_gibbs_run": (_i, [_vp] * 4 + _RUN),
     "ey_philox_uniform_blocks": (_i, [_vp, _i64, _i64, _u64, _u64, _u64, _i, _vp]),
     "ey_inse_univariate": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "ey_plan_attach_da": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _i]),

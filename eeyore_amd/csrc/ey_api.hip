@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "ey_common.h"
@@ -732,113 +733,9 @@ int ey_log_target_grad(ey_plan* pl, const void* theta, const void* temp, int64_t
   return ey_generic_log_target(pl, theta, temp, C, nullptr, nullptr, target, grad, (hipStream_t)stream);
 }
 
-int ey_hmc_step(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                uint64_t chain_offset, uint32_t flags, void* accepted, void* accept_rate, void* H_cur, void* H_prop,
-                void* stream) {
-  int rc = check_ready(pl, C, "ey_hmc_step", 3);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, "ey_hmc_step: null argument");
-  if (L < 1) EY_FAIL(EY_ERR_INVALID, "ey_hmc_step: num_steps must be >= 1");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, "ey_hmc_step"))) return rc;
-  const bool fused = (use_mfma32(pl) || use_fused16(pl)) && !(flags & EY_FORCE_GENERIC);
-  if ((rc = da_check(pl, C, fused, "ey_hmc_step"))) return rc;
-  EY_HIP(hipSetDevice(pl->device));
-  const EyDA da = da_window(pl, 1);
-  if (da.step) step_vec = da.step;  // every kernel family: the attached step vector is the step
-  if (use_mfma32(pl) && !(flags & EY_FORCE_GENERIC)) {  // accumulates attached moments itself
-    rc = ey_mfma32_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                       accepted, accept_rate, H_cur, H_prop, (hipStream_t)stream, nullptr, &da);
-    if (rc == EY_OK && da.state) pl->da_done += 1;  // the table advances only past iterations that were launched
-    return rc;
-  }
-  if (use_fused16(pl) && !(flags & EY_FORCE_GENERIC)) {
-    rc = ey_fused16_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                        accepted, accept_rate, H_cur, H_prop, (hipStream_t)stream, nullptr, &da);
-    if (rc == EY_OK && da.state) pl->da_done += 1;
-  }
-  else if (use_large(pl, 3, flags))
-    rc = ey_large_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                      accepted, accept_rate, H_cur, H_prop, (hipStream_t)stream);
-  else
-    rc = ey_generic_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                        accepted, accept_rate, H_cur, H_prop, (hipStream_t)stream);
-  return moments_trailing(pl, rc, theta, accepted, C, stream);
-}
-
 __global__ void k_count_accepts(const unsigned char* __restrict__ accepted, int* __restrict__ count, int64_t C) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C && accepted[c]) count[c] += 1;
-}
-
-int ey_hmc_run(ey_plan* pl, void* theta, void* target, void* grad, double step, const void* step_vec, int L,
-               const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
-               int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
-               void* stream) {
-  int rc = check_ready(pl, C, "ey_hmc_run", 3);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, "ey_hmc_run: null argument");
-  if (L < 1) EY_FAIL(EY_ERR_INVALID, "ey_hmc_run: num_steps must be >= 1");
-  if (n_iters < 1) EY_FAIL(EY_ERR_INVALID, "ey_hmc_run: n_iters must be >= 1");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, "ey_hmc_run"))) return rc;
-  const bool f16 = use_fused16(pl) && !(flags & EY_FORCE_GENERIC);
-  const bool m32 = use_mfma32(pl) && !(flags & EY_FORCE_GENERIC);
-  if ((rc = da_check(pl, C, f16 || m32, "ey_hmc_run"))) return rc;
-  EY_HIP(hipSetDevice(pl->device));
-  hipStream_t s = (hipStream_t)stream;
-  EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  const EyDA da = da_window(pl, n_iters);
-  if (da.step) step_vec = da.step;
-  if (m32) {
-    rc = ey_mfma32_hmc(pl, theta, target, grad, nullptr, nullptr, step, step_vec, L, temp, C, seed, iter, chain_offset,
-                       flags, accepted, nullptr, nullptr, nullptr, s, &run, &da);
-    if (rc == EY_OK && da.state) pl->da_done += da.n;
-    return rc;
-  }
-  if (f16 || !use_large(pl, 3, flags)) {
-    // the generic kernels do not fuse the moments: they are replayed from the recorded samples, which must then exist
-    // (checked BEFORE the launch: a failure must leave the chains where they were)
-    if (pl->mom_s1 && n_iters > 1 && (!samples || !accepted_rec))
-      EY_FAIL(EY_ERR_UNSUPPORTED, "ey_hmc_run: attached moments with n_iters > 1 need the samples and accepted records "
-                                  "on this kernel family");
-    if (f16) {
-      rc = ey_fused16_hmc(pl, theta, target, grad, nullptr, nullptr, step, step_vec, L, temp, C, seed, iter, chain_offset,
-                          flags, accepted, nullptr, nullptr, nullptr, s, &run, &da);
-      if (rc == EY_OK && da.state) pl->da_done += da.n;
-    } else
-      rc = ey_generic_hmc(pl, theta, target, grad, nullptr, nullptr, step, step_vec, L, temp, C, seed, iter,
-                          chain_offset, flags, accepted, nullptr, nullptr, nullptr, s, &run);
-    if (rc != EY_OK || !pl->mom_s1) return rc;
-    if (n_iters == 1)
-      return ey_stats_update(theta, accepted_rec ? accepted_rec : accepted, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2,
-                             pl->mom_acc, stream);
-    return ey_stats_update_run(samples, accepted_rec, n_iters, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, pl->mom_acc,
-                               stream);
-  }
-  // models beyond LDS: the layerwise path has no in-kernel iteration loop; the launches are queued back to back
-  const size_t es = esize(pl);
-  for (int it = 0; it < n_iters; ++it) {
-    rc = ey_large_hmc(pl, theta, target, grad, nullptr, nullptr, step, step_vec, L, temp, C, seed, iter + it,
-                      chain_offset, flags, accepted, nullptr, nullptr, nullptr, s);
-    if (rc) return rc;
-    if (samples)
-      EY_HIP(hipMemcpyAsync((char*)samples + (size_t)it * C * pl->m.P * es, theta, (size_t)C * pl->m.P * es,
-                            hipMemcpyDeviceToDevice, s));
-    if (targets)
-      EY_HIP(hipMemcpyAsync((char*)targets + (size_t)it * C * es, target, (size_t)C * es, hipMemcpyDeviceToDevice, s));
-    if (accepted_rec)
-      EY_HIP(hipMemcpyAsync((char*)accepted_rec + (size_t)it * C, accepted, (size_t)C, hipMemcpyDeviceToDevice, s));
-    if (accept_count)
-      hipLaunchKernelGGL(k_count_accepts, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s,
-                         (const unsigned char*)accepted, (int*)accept_count, C);
-    if ((rc = moments_trailing(pl, EY_OK, theta, accepted, C, stream))) return rc;
-  }
-  EY_HIP(hipGetLastError());
-  return EY_OK;
 }
 
 int ey_hmc_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
@@ -891,255 +788,298 @@ static int record_iteration(ey_plan* pl, const EyRun* run, int it, const void* t
   return EY_OK;
 }
 
-static int mala_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                     const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                     uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate, void* stream,
-                     const EyRun* run, const char* who) {
-  int rc = check_ready(pl, C, who, 4);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !grad || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (!(step > 0.0) && !step_vec) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": step must be positive");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  EY_HIP(hipSetDevice(pl->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (use_mfma32(pl) && !(flags & EY_FORCE_GENERIC))
-    return ey_mfma32_mala(pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter, chain_offset, accepted,
-                          log_rate, s, run);
-  const bool f16 = use_fused16(pl) && !(flags & EY_FORCE_GENERIC);
-  if (f16 || !use_large(pl, 4, flags)) {  // k_mala carves four state vectors from LDS
-    if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
-    rc = f16 ? ey_fused16_mala(pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter, chain_offset, accepted,
-                               log_rate, s, run)
-             : ey_generic_mala(pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter, chain_offset, accepted,
-                               log_rate, s, run);
-    return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+}  // extern "C": the frame below holds templates
+
+// ---- the sampler entry points.  Each is its *_impl with the ABI's arguments packed, and every *_impl
+// runs in one frame:  begin()  ->  the sampler's own argument checks  ->  ready()  ->  the launch  ->  finish().
+#define EY_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)
+struct EyCall {
+  ey_plan* pl;
+  const EyDraw& d;
+  const char* who;
+  std::optional<EyVariantScope> vs;
+
+  // the plan can serve the batch (nvec: the state vectors its generic kernel keeps in LDS), under the plan's variant;
+  // 1 = an empty batch, which is answered OK before any buffer is looked at (done())
+  int begin(int nvec = 2) {
+    const int rc = check_ready(pl, d.C, who, nvec);
+    if (rc == EY_OK) vs.emplace(pl);
+    return rc;
   }
-  const int n = run ? run->n_iters : 1;
-  for (int it = 0; it < n; ++it) {  // models beyond LDS: launches queued back to back
-    rc = ey_large_mala_mh(pl, theta, target, grad, z, u, step, step_vec, nullptr, temp, C, seed, iter + it,
-                          chain_offset, accepted, log_rate, s);
-    if (rc) return rc;
-    if (run && (rc = record_iteration(pl, run, it, theta, target, accepted, C, s))) return rc;
-    if ((rc = moments_trailing(pl, EY_OK, theta, accepted, C, stream))) return rc;
+  // the attached moments fit the call -- replayed: on a family that replays them from the records, which must then
+  // exist (before the launch: a failure leaves the chains alone) -- and the plan's device is current
+  int ready(bool replayed) {
+    EY_TRY(moments_check(pl, d.C, who));
+    if (replayed) EY_TRY(moments_replay_check(pl, d.run, who));
+    EY_HIP(hipSetDevice(pl->device));
+    return EY_OK;
+  }
+  // the moments of a family that does not fuse them, from the state (one draw) or the records (a run) the launch left
+  int finish(int rc, const void* theta) {
+    return rc ? rc : moments_replay(pl, d.run, theta, d.accepted, d.C, who, d.s);
+  }
+  int refuse(const char* what) const { EY_FAIL(EY_ERR_INVALID, std::string(who) + ": " + what); }
+  int n_iters() const { return d.run && d.run->n_iters < 1 ? refuse("n_iters must be >= 1") : EY_OK; }
+  int step(double step, const void* step_vec) const {
+    return !(step > 0.0) && !step_vec ? refuse("step must be positive") : EY_OK;
+  }
+  int factors(int64_t G, const void* tril_index) const {
+    if (G < 1) return refuse("the number of factors G must be >= 1");
+    return !tril_index && G != 1 && G != d.C ? refuse("without tril_index, G must be 1 or the number of chains") : EY_OK;
+  }
+};
+static int done(int rc) { return rc < 0 ? rc : EY_OK; }
+
+// the kernel family that serves a draw of this plan (nvec as in use_large)
+enum EyFamily { FAM_MFMA32, FAM_FUSED16, FAM_GENERIC, FAM_LARGE };
+static EyFamily family_of(const ey_plan* pl, int nvec, uint32_t flags) {
+  if (use_mfma32(pl) && !(flags & EY_FORCE_GENERIC)) return FAM_MFMA32;
+  if (use_fused16(pl) && !(flags & EY_FORCE_GENERIC)) return FAM_FUSED16;
+  return use_large(pl, nvec, flags) ? FAM_LARGE : FAM_GENERIC;
+}
+static bool replays_moments(EyFamily f) { return f == FAM_FUSED16 || f == FAM_GENERIC; }  // mfma32 fuses, large trails
+
+// Models beyond LDS: the layerwise path has no in-kernel iteration loop.  launch(one) queues one iteration; its records
+// and the trailing moments pass follow it on the stream, iteration by iteration.
+template <typename F>
+static int large_loop(ey_plan* pl, const EyDraw& d, const void* theta, const void* target, F launch) {
+  EyDraw one = d;
+  one.run = nullptr;
+  for (int it = 0, n = d.run ? d.run->n_iters : 1; it < n; ++it) {
+    one.iter = d.iter + it;
+    EY_TRY(launch(one));
+    if (d.run) EY_TRY(record_iteration(pl, d.run, it, theta, target, d.accepted, d.C, d.s));
+    EY_TRY(moments_trailing(pl, EY_OK, theta, d.accepted, d.C, d.s));
   }
   EY_HIP(hipGetLastError());
   return EY_OK;
 }
 
+static int hmc_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
+                    const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin(3)) return done(rc);
+  if (!theta || !target || !grad || !d.accepted) return f.refuse("null argument");
+  if (L < 1) return f.refuse("num_steps must be >= 1");
+  EY_TRY(f.n_iters());
+  const EyFamily fam = family_of(pl, 3, d.flags);
+  // the dual averaging is checked between the moments and their records, as it always was: ready() stops before
+  // the records
+  EY_TRY(f.ready(false));
+  EY_TRY(da_check(pl, d.C, fam == FAM_MFMA32 || fam == FAM_FUSED16, who));
+  if (replays_moments(fam)) EY_TRY(moments_replay_check(pl, d.run, who));
+  const EyDA da = da_window(pl, d.run ? d.run->n_iters : 1);
+  if (da.step) step_vec = da.step;  // every kernel family: the attached step vector is the step
+  if (fam == FAM_LARGE)
+    return large_loop(pl, d, theta, target, [&](const EyDraw& one) {
+      return ey_large_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, one, rate, hcur, hprop);
+    });
+  if (fam == FAM_GENERIC)
+    return f.finish(ey_generic_hmc(pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur, hprop), theta);
+  const int rc = (fam == FAM_MFMA32 ? ey_mfma32_hmc : ey_fused16_hmc)(pl, theta, target, grad, p0, u, step, step_vec, L, d,
+                                                                     rate, hcur, hprop, &da);
+  if (rc == EY_OK && da.state) pl->da_done += da.n;  // the table advances only past iterations that were launched
+  return fam == FAM_MFMA32 ? rc : f.finish(rc, theta);  // mfma32 accumulates attached moments itself
+}
+
+static int mala_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
+                     const void* step_vec, const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin(4)) return done(rc);  // k_mala carves four state vectors from LDS
+  if (!theta || !target || !grad || !d.accepted) return f.refuse("null argument");
+  EY_TRY(f.step(step, step_vec));
+  EY_TRY(f.n_iters());
+  const EyFamily fam = family_of(pl, 4, d.flags);
+  EY_TRY(f.ready(replays_moments(fam)));
+  if (fam == FAM_MFMA32) return ey_mfma32_mala(pl, theta, target, grad, z, u, step, step_vec, d);
+  if (fam == FAM_LARGE)
+    return large_loop(pl, d, theta, target, [&](const EyDraw& one) {
+      return ey_large_mala_mh(pl, theta, target, grad, z, u, step, step_vec, nullptr, one);
+    });
+  return f.finish((fam == FAM_FUSED16 ? ey_fused16_mala : ey_generic_mala)(pl, theta, target, grad, z, u, step, step_vec, d),
+                  theta);
+}
+
 static int mh_impl(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                   const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
-                   void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
-  int rc = check_ready(pl, C, who);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !scale || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  EY_HIP(hipSetDevice(pl->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (use_mfma32(pl) && !(flags & EY_FORCE_GENERIC))
-    return ey_mfma32_mh(pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
-  const bool f16 = use_fused16(pl) && !(flags & EY_FORCE_GENERIC);
-  if (f16 || !use_large(pl, 2, flags)) {
-    if ((rc = moments_replay_check(pl, run, who))) return rc;
-    rc = f16 ? ey_fused16_mh(pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run)
-             : ey_generic_mh(pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
-    return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+                   const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !scale || !d.accepted) return f.refuse("null argument");
+  EY_TRY(f.n_iters());
+  const EyFamily fam = family_of(pl, 2, d.flags);
+  EY_TRY(f.ready(replays_moments(fam)));
+  if (fam == FAM_MFMA32) return ey_mfma32_mh(pl, theta, target, z, u, scale, d);
+  if (fam == FAM_LARGE)
+    return large_loop(pl, d, theta, target, [&](const EyDraw& one) {
+      return ey_large_mala_mh(pl, theta, target, nullptr, z, u, 0.0, nullptr, scale, one);
+    });
+  return f.finish((fam == FAM_FUSED16 ? ey_fused16_mh : ey_generic_mh)(pl, theta, target, z, u, scale, d), theta);
+}
+
+// RAM, MH and MALA with a fixed factor, and AM run on their own kernels of ey_generic.hip for every model, whatever
+// plan.kernel says: the fused families have nowhere to keep a factor, let alone adapt one
+static int ram_impl(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
+                    uint64_t n, const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !chol || !d.accepted) return f.refuse("null argument");
+  EY_TRY(f.n_iters());
+  if (n == 0) return f.refuse("the adaptation index n must be >= 1");
+  if (!(a > 0.0 && a < 1.0)) return f.refuse("the target acceptance a must lie in (0, 1)");
+  if (!std::isfinite(g)) return f.refuse("the decay exponent g must be finite");
+  EY_TRY(f.ready(true));
+  return f.finish(ey_generic_ram(pl, theta, target, chol, z, u, a, g, n, d), theta);
+}
+
+static int mh_tril_impl(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
+                        const void* z, const void* u, const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !tril || !d.accepted) return f.refuse("null argument");
+  EY_TRY(f.n_iters());
+  EY_TRY(f.factors(G, tril_index));
+  EY_TRY(f.ready(true));
+  return f.finish(ey_generic_mh_tril(pl, theta, target, tril, G, tril_index, z, u, d), theta);
+}
+
+static int mala_tril_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
+                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
+                          const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !grad || !tril || !d.accepted) return f.refuse("null argument");
+  EY_TRY(f.step(step, step_vec));
+  EY_TRY(f.n_iters());
+  EY_TRY(f.factors(G, tril_index));
+  EY_TRY(f.ready(true));
+  return f.finish(ey_generic_mala_tril(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, d), theta);
+}
+
+static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, const char* who,
+                   int transform) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !am.mean || !am.cov_sum || !am.cov || !am.num_accepted || !am.cov0 || !d.accepted ||
+      !am.breakdowns)
+    return f.refuse("null argument");
+  EY_TRY(f.n_iters());
+  if (am.t0 < 2) return f.refuse("t0 must be >= 2 (the covariance divides by n - 1)");
+  if (!(am.l >= 0.0 && am.l <= 1.0)) return f.refuse("the mixture weight l must lie in [0, 1]");
+  if (!std::isfinite(am.b) || !std::isfinite(am.c)) return f.refuse("b and c must be finite");
+  if (transform == EY_AM_SOFTABS) {  // am.eps carries a
+    if (!(std::isfinite(am.eps) && am.eps > 0.0)) return f.refuse("a must be finite and > 0");
+  } else if (!(std::isfinite(am.eps) && am.eps >= 0.0)) {
+    return f.refuse("eps must be finite and >= 0");
   }
-  const int n = run ? run->n_iters : 1;
-  for (int it = 0; it < n; ++it) {
-    rc = ey_large_mala_mh(pl, theta, target, nullptr, z, u, 0.0, nullptr, scale, temp, C, seed, iter + it, chain_offset,
-                          accepted, log_rate, s);
-    if (rc) return rc;
-    if (run && (rc = record_iteration(pl, run, it, theta, target, accepted, C, s))) return rc;
-    if ((rc = moments_trailing(pl, EY_OK, theta, accepted, C, stream))) return rc;
-  }
-  EY_HIP(hipGetLastError());
-  return EY_OK;
+  if (am.idx < 0 || am.idx + 1 - am.offset < 1)
+    return f.refuse("idx must be >= 0 and the adaptation index idx + 1 - offset >= 1");
+  EY_TRY(f.ready(true));
+  return f.finish(ey_generic_am(pl, theta, target, am, d, transform), theta);
+}
+// the state and the settings of the four AM entry points (eps: the ridge, or softabs's a)
+static EyAm make_am(void* running_mean, void* cov_sum, void* cov, void* num_accepted, const void* cov0, int cov0_per_chain,
+                    double l, double b, double c, double eps, int64_t t0, int64_t idx, int64_t offset, void* breakdowns,
+                    const void* z = nullptr, const void* u_mix = nullptr, const void* u = nullptr, void* branch = nullptr) {
+  return {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0, idx, offset,
+          z, u_mix, u, (unsigned char*)branch, (int*)breakdowns};
+}
+
+extern "C" {
+
+int ey_hmc_step(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
+                const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
+                uint64_t chain_offset, uint32_t flags, void* accepted, void* accept_rate, void* H_cur, void* H_prop,
+                void* stream) {
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, nullptr};
+  return hmc_impl(pl, theta, target, grad, p0, u, step, step_vec, L, d, accept_rate, H_cur, H_prop, "ey_hmc_step");
+}
+
+int ey_hmc_run(ey_plan* pl, void* theta, void* target, void* grad, double step, const void* step_vec, int L,
+               const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+               int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
+               void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return hmc_impl(pl, theta, target, grad, nullptr, nullptr, step, step_vec, L, d, nullptr, nullptr, nullptr, "ey_hmc_run");
 }
 
 int ey_mala_step(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
                  const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                  uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate, void* stream) {
-  return mala_impl(pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter, chain_offset, flags, accepted,
-                   log_rate, stream, nullptr, "ey_mala_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return mala_impl(pl, theta, target, grad, z, u, step, step_vec, d, "ey_mala_step");
 }
 
 int ey_mala_run(ey_plan* pl, void* theta, void* target, void* grad, double step, const void* step_vec, const void* temp,
                 int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
                 void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return mala_impl(pl, theta, target, grad, nullptr, nullptr, step, step_vec, temp, C, seed, iter, chain_offset, flags,
-                   accepted, nullptr, stream, &run, "ey_mala_run");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return mala_impl(pl, theta, target, grad, nullptr, nullptr, step, step_vec, d, "ey_mala_run");
 }
 
 int ey_mh_step(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
                const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                void* accepted, void* log_rate, void* stream) {
-  return mh_impl(pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset, flags, accepted, log_rate, stream,
-                 nullptr, "ey_mh_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return mh_impl(pl, theta, target, z, u, scale, d, "ey_mh_step");
 }
 
 int ey_mh_run(ey_plan* pl, void* theta, void* target, const void* scale, const void* temp, int64_t C, uint64_t seed,
               uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets,
               void* accepted_rec, void* accept_count, void* accepted, void* stream) {
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return mh_impl(pl, theta, target, nullptr, nullptr, scale, temp, C, seed, iter, chain_offset, flags, accepted, nullptr,
-                 stream, &run, "ey_mh_run");
-}
-
-// RAM runs on k_ram (ey_generic.hip) for every model: the fused families have no factor to adapt
-static int ram_impl(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
-                    uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                    void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
-  int rc = check_ready(pl, C, who);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !chol || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (n == 0) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the adaptation index n must be >= 1");
-  if (!(a > 0.0 && a < 1.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the target acceptance a must lie in (0, 1)");
-  if (!std::isfinite(g)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the decay exponent g must be finite");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
-  EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_ram(pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted, log_rate,
-                      (hipStream_t)stream, run);
-  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return mh_impl(pl, theta, target, nullptr, nullptr, scale, d, "ey_mh_run");
 }
 
 int ey_ram_step(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
                 uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
                 uint32_t flags, void* accepted, void* log_rate, void* stream) {
-  (void)flags;
-  return ram_impl(pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter, chain_offset, accepted, log_rate, stream,
-                  nullptr, "ey_ram_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return ram_impl(pl, theta, target, chol, z, u, a, g, n, d, "ey_ram_step");
 }
 
 int ey_ram_run(ey_plan* pl, void* theta, void* target, void* chol, double a, double g, uint64_t n, const void* temp,
                int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters,
                void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
-  (void)flags;
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return ram_impl(pl, theta, target, chol, nullptr, nullptr, a, g, n, temp, C, seed, iter, chain_offset, accepted,
-                  nullptr, stream, &run, "ey_ram_run");
-}
-
-// MH with a fixed factor runs on k_mh_tril (ey_generic.hip) for every model: the fused families have nowhere to keep one
-static int mh_tril_impl(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
-                        const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                        uint64_t chain_offset, void* accepted, void* log_rate, void* stream, const EyRun* run,
-                        const char* who) {
-  int rc = check_ready(pl, C, who);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !tril || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (G < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the number of factors G must be >= 1");
-  if (!tril_index && G != 1 && G != C)
-    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": without tril_index, G must be 1 or the number of chains");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
-  EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_mh_tril(pl, theta, target, tril, G, tril_index, z, u, temp, C, seed, iter, chain_offset, accepted,
-                          log_rate, (hipStream_t)stream, run);
-  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return ram_impl(pl, theta, target, chol, nullptr, nullptr, a, g, n, d, "ey_ram_run");
 }
 
 int ey_mh_tril_step(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                     const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                     uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate, void* stream) {
-  (void)flags;
-  return mh_tril_impl(pl, theta, target, tril, G, tril_index, z, u, temp, C, seed, iter, chain_offset, accepted, log_rate,
-                      stream, nullptr, "ey_mh_tril_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return mh_tril_impl(pl, theta, target, tril, G, tril_index, z, u, d, "ey_mh_tril_step");
 }
 
 int ey_mh_tril_run(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                    const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                    int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count, void* accepted,
                    void* stream) {
-  (void)flags;
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return mh_tril_impl(pl, theta, target, tril, G, tril_index, nullptr, nullptr, temp, C, seed, iter, chain_offset,
-                      accepted, nullptr, stream, &run, "ey_mh_tril_run");
-}
-
-// MALA with a fixed factor runs on k_mala_tril (ey_generic.hip) for every model, as MH with one does on k_mh_tril
-static int mala_tril_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
-                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
-                          const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                          void* log_rate, void* stream, const EyRun* run, const char* who) {
-  int rc = check_ready(pl, C, who);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !grad || !tril || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (!(step > 0.0) && !step_vec) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": step must be positive");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (G < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the number of factors G must be >= 1");
-  if (!tril_index && G != 1 && G != C)
-    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": without tril_index, G must be 1 or the number of chains");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
-  EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_mala_tril(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C, seed, iter,
-                            chain_offset, accepted, log_rate, (hipStream_t)stream, run);
-  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return mh_tril_impl(pl, theta, target, tril, G, tril_index, nullptr, nullptr, d, "ey_mh_tril_run");
 }
 
 int ey_mala_tril_step(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                       const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                       void* accepted, void* log_rate, void* stream) {
-  (void)flags;
-  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, temp, C, seed, iter,
-                        chain_offset, accepted, log_rate, stream, nullptr, "ey_mala_tril_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, d, "ey_mala_tril_step");
 }
 
 int ey_mala_tril_run(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                      const void* tril_index, double step, const void* step_vec, const void* temp, int64_t C, uint64_t seed,
                      uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets,
                      void* accepted_rec, void* accept_count, void* accepted, void* stream) {
-  (void)flags;
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, nullptr, nullptr, step, step_vec, temp, C, seed, iter,
-                        chain_offset, accepted, nullptr, stream, &run, "ey_mala_tril_run");
-}
-
-// AM runs on k_am (ey_generic.hip) for every model, as RAM does on k_ram
-static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
-                   uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, void* stream, const EyRun* run,
-                   const char* who, int transform = EY_AM_RIDGE) {
-  int rc = check_ready(pl, C, who);
-  if (rc) return rc < 0 ? rc : EY_OK;
-  EyVariantScope vs(pl);
-  if (!theta || !target || !am.mean || !am.cov_sum || !am.cov || !am.num_accepted || !am.cov0 || !accepted ||
-      !am.breakdowns)
-    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if (run && run->n_iters < 1) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": n_iters must be >= 1");
-  if (am.t0 < 2) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": t0 must be >= 2 (the covariance divides by n - 1)");
-  if (!(am.l >= 0.0 && am.l <= 1.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": the mixture weight l must lie in [0, 1]");
-  if (!std::isfinite(am.b) || !std::isfinite(am.c)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": b and c must be finite");
-  if (transform == EY_AM_SOFTABS) {  // am.eps carries a
-    if (!(std::isfinite(am.eps) && am.eps > 0.0)) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": a must be finite and > 0");
-  } else if (!(std::isfinite(am.eps) && am.eps >= 0.0)) {
-    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": eps must be finite and >= 0");
-  }
-  if (am.idx < 0 || am.idx + 1 - am.offset < 1)
-    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": idx must be >= 0 and the adaptation index idx + 1 - offset >= 1");
-  if (C == 0) return EY_OK;
-  if ((rc = moments_check(pl, C, who))) return rc;
-  if ((rc = moments_replay_check(pl, run, who))) return rc;  // before the launch: a failure leaves the chains alone
-  EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_am(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, (hipStream_t)stream, run,
-                     transform);
-  return rc ? rc : moments_replay(pl, run, theta, accepted, C, who, stream);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, nullptr, nullptr, step, step_vec, d,
+                        "ey_mala_tril_run");
 }
 
 int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,
@@ -1147,11 +1087,9 @@ int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void*
                int64_t offset, const void* z, const void* u_mix, const void* u, const void* temp, int64_t C,
                uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, void* accepted, void* log_rate,
                void* branch, void* breakdowns, void* stream) {
-  (void)flags;
-  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0, idx, offset,
-                   z, u_mix, u, (unsigned char*)branch, (int*)breakdowns};
-  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, stream, nullptr,
-                 "ey_am_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return am_impl(pl, theta, target, make_am(running_mean, cov_sum, cov, num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0,
+                                            idx, offset, breakdowns, z, u_mix, u, branch), d, "ey_am_step", EY_AM_RIDGE);
 }
 
 int ey_am_run(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,
@@ -1159,11 +1097,10 @@ int ey_am_run(ey_plan* pl, void* theta, void* target, void* running_mean, void* 
               int64_t offset, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
               uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count,
               void* accepted, void* breakdowns, void* stream) {
-  (void)flags;
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0, idx, offset,
-                   nullptr, nullptr, nullptr, nullptr, (int*)breakdowns};
-  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, nullptr, stream, &run, "ey_am_run");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return am_impl(pl, theta, target, make_am(running_mean, cov_sum, cov, num_accepted, cov0, cov0_per_chain, l, b, c, eps, t0,
+                                            idx, offset, breakdowns), d, "ey_am_run", EY_AM_RIDGE);
 }
 
 // AM with the transform softabs(cov, a) in place of the ridge: k_am's softabs instantiation
@@ -1172,11 +1109,10 @@ int ey_am_softabs_step(ey_plan* pl, void* theta, void* target, void* running_mea
                        int64_t t0, int64_t idx, int64_t offset, const void* z, const void* u_mix, const void* u,
                        const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                        void* accepted, void* log_rate, void* branch, void* breakdowns, void* stream) {
-  (void)flags;
-  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, a, t0, idx, offset,
-                   z, u_mix, u, (unsigned char*)branch, (int*)breakdowns};
-  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, log_rate, stream, nullptr,
-                 "ey_am_softabs_step", EY_AM_SOFTABS);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return am_impl(pl, theta, target, make_am(running_mean, cov_sum, cov, num_accepted, cov0, cov0_per_chain, l, b, c, a, t0,
+                                            idx, offset, breakdowns, z, u_mix, u, branch), d, "ey_am_softabs_step",
+                 EY_AM_SOFTABS);
 }
 
 int ey_am_softabs_run(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov,
@@ -1184,12 +1120,10 @@ int ey_am_softabs_run(ey_plan* pl, void* theta, void* target, void* running_mean
                       int64_t t0, int64_t idx, int64_t offset, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
                       uint64_t chain_offset, uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec,
                       void* accept_count, void* accepted, void* breakdowns, void* stream) {
-  (void)flags;
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  const EyAm am = {running_mean, cov_sum, cov, (int*)num_accepted, cov0, cov0_per_chain, l, b, c, a, t0, idx, offset,
-                   nullptr, nullptr, nullptr, nullptr, (int*)breakdowns};
-  return am_impl(pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted, nullptr, stream, &run,
-                 "ey_am_softabs_run", EY_AM_SOFTABS);
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return am_impl(pl, theta, target, make_am(running_mean, cov_sum, cov, num_accepted, cov0, cov0_per_chain, l, b, c, a, t0,
+                                            idx, offset, breakdowns), d, "ey_am_softabs_run", EY_AM_SOFTABS);
 }
 
 int ey_am_softabs_fits(const ey_plan* pl) { return pl && ey_generic_am_softabs_fits(pl) ? 1 : 0; }
@@ -1268,12 +1202,15 @@ int ey_gibbs_table_destroy(ey_gibbs_table* tb) {
   return EY_OK;
 }
 
+// Not in the frame of the other samplers (EyCall), because its order is its own: a mixture plan is refused first, the table
+// and its LDS image are checked before an empty batch is answered and the buffers after it, and the kernel itself adds the
+// accepted fractions to the attached acc, so that the moments are replayed without accept flags.
 static int gibbs_impl(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
-                      const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
-                      void* accepted, void* log_rate, void* stream, const EyRun* run, const char* who) {
+                      const EyDraw& d, const char* who) {
+  const EyRun* run = d.run;
   if (pl && is_mix(pl))
     EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": Gibbs blocks are the nodes of an MLP; " + mix_noun(pl) + " has none");
-  int rc = check_ready(pl, C, who);
+  int rc = check_ready(pl, d.C, who);
   if (rc < 0) return rc;
   if (!tb) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null block table");
   if (tb->P != pl->m.P || tb->dtype != pl->dtype || tb->device != pl->device)
@@ -1284,34 +1221,33 @@ static int gibbs_impl(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* 
                                                    "160 KiB LDS of a CU");
   if (rc) return EY_OK;  // C == 0
   EyVariantScope vs(pl);
-  if (!theta || !target || !accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
-  if ((rc = moments_check(pl, C, who))) return rc;
+  if (!theta || !target || !d.accepted) EY_FAIL(EY_ERR_INVALID, std::string(who) + ": null argument");
+  if ((rc = moments_check(pl, d.C, who))) return rc;
   if (pl->mom_s1 && run && run->n_iters > 1 && !run->samples)
     EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": attached moments with n_iters > 1 need the samples record");
   EY_HIP(hipSetDevice(pl->device));
-  rc = ey_generic_gibbs(pl, tb, theta, target, z, u, (flags & EY_GIBBS_CARRY) != 0, temp, C, seed, iter, chain_offset,
-                        accepted, log_rate, pl->mom_s1 ? pl->mom_acc : nullptr, (hipStream_t)stream, run);
+  rc = ey_generic_gibbs(pl, tb, theta, target, z, u, d, pl->mom_s1 ? pl->mom_acc : nullptr);
   if (rc || !pl->mom_s1) return rc;
   // s1, s2 from the state(s) the draws left; the kernel has added the accepted fractions to acc
   if (!run || run->n_iters == 1)
-    return ey_stats_update(theta, nullptr, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr, stream);
-  return ey_stats_update_run(run->samples, nullptr, run->n_iters, C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr,
-                             stream);
+    return ey_stats_update(theta, nullptr, d.C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr, d.s);
+  return ey_stats_update_run(run->samples, nullptr, run->n_iters, d.C, pl->m.P, pl->dtype, pl->mom_s1, pl->mom_s2, nullptr,
+                             d.s);
 }
 
 int ey_gibbs_step(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
                   const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
                   void* accepted, void* log_rate, void* stream) {
-  return gibbs_impl(pl, tb, theta, target, z, u, temp, C, seed, iter, chain_offset, flags, accepted, log_rate, stream,
-                    nullptr, "ey_gibbs_step");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, log_rate, (hipStream_t)stream, nullptr};
+  return gibbs_impl(pl, tb, theta, target, z, u, d, "ey_gibbs_step");
 }
 
 int ey_gibbs_run(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* temp, int64_t C,
                  uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
                  void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
   const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
-  return gibbs_impl(pl, tb, theta, target, nullptr, nullptr, temp, C, seed, iter, chain_offset, flags, accepted, nullptr,
-                    stream, &run, "ey_gibbs_run");
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return gibbs_impl(pl, tb, theta, target, nullptr, nullptr, d, "ey_gibbs_run");
 }
 
 }  // extern "C"

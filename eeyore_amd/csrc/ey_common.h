@@ -168,6 +168,20 @@ struct EyRun {
   int* accept_count;  // [C] int32 (+=), or null
 };
 
+// One draw of every chain (or, with `run`, a run of draws) as every sampler launcher takes it: what the entry points of all
+// samplers share, named, so that no two of these can change places unnoticed.  HMC writes rate / hcur / hprop instead of
+// log_rate; the launchers of the layerwise path queue one iteration and read no `run`.
+struct EyDraw {
+  const void* temp;  // [C] tempering weights, or null
+  int64_t C;
+  uint64_t seed, iter, chain_offset;  // the Philox key of the first iteration
+  uint32_t flags;
+  void* accepted;    // [C] uint8 (Gibbs: [C, S])
+  void* log_rate;    // [C] (Gibbs: [C, S]), or null
+  hipStream_t s;
+  const EyRun* run;  // the records of a *_run call; null: one draw, nothing recorded
+};
+
 // the attached moments from the records of a launch, in one streaming pass (ey_api.hip)
 int ey_stats_update_run(const void* samples, const void* accepted_rec, int n_it, int64_t C, int64_t P, int dtype, void* s1,
                         void* s2, void* acc, void* stream);
@@ -186,33 +200,26 @@ void ey_generic_tilt_scratch(EyModel& m);  // ... of an EY_KIND_TILT model: none
 int ey_generic_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
 int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hipStream_t s);  // out [C, N, dK] (ey_forward)
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                   const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                   hipStream_t s, const EyRun* run = nullptr);
+                   const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop);
 int ey_generic_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                         int64_t C, void* target, void* grad, hipStream_t s);
 int ey_generic_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                    const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                    uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                    const void* step_vec, const EyDraw& d);
 int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                  void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                  const EyDraw& d);
 // robust adaptive Metropolis (k_ram): every model whose factor fits beside the evaluation image, whatever plan.kernel says
 size_t ey_generic_ram_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
 int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
-                   uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                   void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                   uint64_t n, const EyDraw& d);
 // MH with a fixed lower-triangular proposal factor (k_mh_tril): as RAM, whatever plan.kernel says
 size_t ey_generic_mh_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
 int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
-                       const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                       const void* z, const void* u, const EyDraw& d);
 // MALA with a fixed lower-triangular proposal factor (k_mala_tril): as k_mh_tril, whatever plan.kernel says
 size_t ey_generic_mala_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain's workgroup
 int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
-                         const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                         void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                         const EyDraw& d);
 
 #define EY_AM_RIDGE 0
 #define EY_AM_SOFTABS 1
@@ -234,9 +241,7 @@ size_t ey_generic_am_lds(const ey_plan* pl, int transform = EY_AM_RIDGE);  // dy
 bool ey_generic_am_softabs_fits(const ey_plan* pl);  // P <= 128 and the softabs instantiation's LDS fits a CU
 // softabs of B dense symmetric [P, P] matrices (k_softabs), the device function k_am's softabs instantiation runs
 int ey_generic_softabs(const void* A, int64_t B, int P, int dtype, double a, void* out, void* sweeps, hipStream_t s);
-int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
-                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
-                  const EyRun* run = nullptr, int transform = EY_AM_RIDGE);
+int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, int transform);
 
 // node-blocked Metropolis-within-Gibbs (k_gibbs): blockwise random-walk Metropolis over a table of disjoint index sets
 struct ey_gibbs_table {
@@ -249,20 +254,16 @@ struct ey_gibbs_table {
 };
 size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb);  // dynamic LDS of one chain's workgroup
 int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
-                     bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                     void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run = nullptr);
+                     const EyDraw& d, double* mom_acc);  // EY_GIBBS_CARRY of d.flags: mode 'reference'
 
 // layerwise batched-GEMM kernels for large models, f32 (ey_large.hip)
 bool ey_large_needed(const ey_plan* pl, int nvec = 3);  // true when the generic kernels cannot hold the model in LDS
 int ey_large_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                         void* target, void* grad, hipStream_t s);
 int ey_large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                 const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                 uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                 hipStream_t s);
+                 const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop);
 int ey_large_mala_mh(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                     const void* step_vec, const void* scale, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                     uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s);
+                     const void* step_vec, const void* scale, const EyDraw& d);
 int ey_large_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                       int64_t C, void* target, void* grad, hipStream_t s);
 int ey_large_log_lik_rows(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* rows, hipStream_t s);
@@ -274,17 +275,13 @@ bool ey_mfma32_supports(const ey_plan* pl);
 int ey_mfma32_kind(const ey_plan* pl);  // 1 the headline model, 2 served in the bf16x3 form only, 0 not served
 int ey_mfma32_set_data(ey_plan* pl, hipStream_t s);
 int ey_mfma32_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                  const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                  uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                  hipStream_t s, const EyRun* run = nullptr, const EyDA* da = nullptr);
+                  const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const EyDA* da);
 int ey_mfma32_log_target_grad(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* target, void* grad,
                               hipStream_t s);
 int ey_mfma32_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                   const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                   const void* step_vec, const EyDraw& d);
 int ey_mfma32_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                 const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                 void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                 const EyDraw& d);
 int ey_mfma32_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,
                        int64_t C, void* target, void* grad, hipStream_t s);
 
@@ -292,15 +289,11 @@ int ey_mfma32_leapfrog(ey_plan* pl, void* theta, void* p, double step, const voi
 bool ey_fused16_supports(const ey_plan* pl);
 int ey_fused16_set_data(ey_plan* pl, hipStream_t s);
 int ey_fused16_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                   const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                   hipStream_t s, const EyRun* run = nullptr, const EyDA* da = nullptr);
+                   const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const EyDA* da);
 int ey_fused16_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                    const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                    uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                    const void* step_vec, const EyDraw& d);
 int ey_fused16_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                  void* log_rate, hipStream_t s, const EyRun* run = nullptr);
+                  const EyDraw& d);
 int ey_fused16_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                           void* target, void* grad, hipStream_t s);
 int ey_fused16_leapfrog(ey_plan* pl, void* theta, void* p, double step, const void* step_vec, int L, const void* temp,

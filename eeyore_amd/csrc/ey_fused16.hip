@@ -1367,8 +1367,12 @@ static int f16_launch(ey_plan* pl, F16Args<T>& a, hipStream_t s) {
   }
 }
 
+// what every sampler mode takes of the draw: the batch, the Philox key, the accept flags and the records of a run
 template <typename T>
-static void f16_set_run(F16Args<T>& a, const EyRun* run) {
+static void f16_set_draw(F16Args<T>& a, const EyDraw& d) {
+  a.C = d.C; a.temp = (const T*)d.temp; a.seed = d.seed; a.iter = d.iter; a.chain_offset = d.chain_offset;
+  a.accepted = (unsigned char*)d.accepted;
+  const EyRun* run = d.run;
   a.n_iters = 1;
   if (run) {
     a.n_iters = run->n_iters;
@@ -1381,9 +1385,7 @@ static void f16_set_run(F16Args<T>& a, const EyRun* run) {
 
 template <typename T>
 static int f16_hmc_t(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                     const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                     uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                     hipStream_t s, const EyRun* run, const EyDA* da) {
+                     const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const EyDA* da) {
   F16Args<T> a = {};
   a.mode = F16_HMC;
   if (da && da->state) {
@@ -1392,55 +1394,40 @@ static int f16_hmc_t(ey_plan* pl, void* theta, void* target, void* grad, const v
   }
   // while a dual averaging is attached its step vector is THE step, also once its table is used up (include/eeyore_amd.h)
   if (da && da->step) step_vec = da->step;
-  a.C = C; a.theta = (T*)theta; a.target = (T*)target; a.grad = (T*)grad; a.p0 = (const T*)p0; a.u = (const T*)u;
-  a.step = (T)step; a.step_vec = (const T*)step_vec; a.L = L; a.temp = (const T*)temp; a.seed = seed; a.iter = iter;
-  a.chain_offset = chain_offset; a.recompute = (flags & EY_RECOMPUTE_INITIAL_GRAD) ? 1 : 0;
-  a.accepted = (unsigned char*)accepted; a.rate = (T*)rate; a.hcur = (T*)hcur; a.hprop = (T*)hprop;
-  f16_set_run(a, run);
-  return f16_launch<T>(pl, a, s);
+  a.theta = (T*)theta; a.target = (T*)target; a.grad = (T*)grad; a.p0 = (const T*)p0; a.u = (const T*)u;
+  a.step = (T)step; a.step_vec = (const T*)step_vec; a.L = L; a.rate = (T*)rate; a.hcur = (T*)hcur; a.hprop = (T*)hprop;
+  a.recompute = (d.flags & EY_RECOMPUTE_INITIAL_GRAD) ? 1 : 0;
+  f16_set_draw(a, d);
+  return f16_launch<T>(pl, a, d.s);
 }
 int ey_fused16_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                   const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                   hipStream_t s, const EyRun* run, const EyDA* da) {
+                   const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const EyDA* da) {
   if (pl->dtype == EY_F32)
-    return f16_hmc_t<float>(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                            accepted, rate, hcur, hprop, s, run, da);
-  return f16_hmc_t<double>(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags,
-                           accepted, rate, hcur, hprop, s, run, da);
+    return f16_hmc_t<float>(pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur, hprop, da);
+  return f16_hmc_t<double>(pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur, hprop, da);
 }
 
 template <typename T>
 static int f16_mala_mh_t(ey_plan* pl, int mode, void* theta, void* target, void* grad, const void* z, const void* u,
-                         double step, const void* step_vec, const void* scale, const void* temp, int64_t C,
-                         uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate,
-                         hipStream_t s, const EyRun* run) {
+                         double step, const void* step_vec, const void* scale, const EyDraw& d) {
   F16Args<T> a = {};
   a.mode = mode;
-  a.C = C; a.theta = (T*)theta; a.target = (T*)target; a.grad = (T*)(grad ? grad : theta); a.p0 = (const T*)z;
+  a.theta = (T*)theta; a.target = (T*)target; a.grad = (T*)(grad ? grad : theta); a.p0 = (const T*)z;
   a.u = (const T*)u; a.step = (T)step; a.sqrt_step = (T)sqrt(step); a.step_vec = (const T*)step_vec;
-  a.scale = (const T*)scale; a.temp = (const T*)temp; a.seed = seed; a.iter = iter; a.chain_offset = chain_offset;
-  a.accepted = (unsigned char*)accepted; a.rate = (T*)log_rate;
-  f16_set_run(a, run);
-  return f16_launch<T>(pl, a, s);
+  a.scale = (const T*)scale; a.rate = (T*)d.log_rate;
+  f16_set_draw(a, d);
+  return f16_launch<T>(pl, a, d.s);
 }
 int ey_fused16_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                    const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                    uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                    const void* step_vec, const EyDraw& d) {
   if (pl->dtype == EY_F32)
-    return f16_mala_mh_t<float>(pl, F16_MALA, theta, target, grad, z, u, step, step_vec, nullptr, temp, C, seed, iter,
-                                chain_offset, accepted, log_rate, s, run);
-  return f16_mala_mh_t<double>(pl, F16_MALA, theta, target, grad, z, u, step, step_vec, nullptr, temp, C, seed, iter,
-                               chain_offset, accepted, log_rate, s, run);
+    return f16_mala_mh_t<float>(pl, F16_MALA, theta, target, grad, z, u, step, step_vec, nullptr, d);
+  return f16_mala_mh_t<double>(pl, F16_MALA, theta, target, grad, z, u, step, step_vec, nullptr, d);
 }
 int ey_fused16_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                  void* log_rate, hipStream_t s, const EyRun* run) {
-  if (pl->dtype == EY_F32)
-    return f16_mala_mh_t<float>(pl, F16_MH, theta, target, nullptr, z, u, 0.0, nullptr, scale, temp, C, seed, iter,
-                                chain_offset, accepted, log_rate, s, run);
-  return f16_mala_mh_t<double>(pl, F16_MH, theta, target, nullptr, z, u, 0.0, nullptr, scale, temp, C, seed, iter,
-                               chain_offset, accepted, log_rate, s, run);
+                  const EyDraw& d) {
+  if (pl->dtype == EY_F32) return f16_mala_mh_t<float>(pl, F16_MH, theta, target, nullptr, z, u, 0.0, nullptr, scale, d);
+  return f16_mala_mh_t<double>(pl, F16_MH, theta, target, nullptr, z, u, 0.0, nullptr, scale, d);
 }
 
 template <typename T>

@@ -1211,6 +1211,10 @@ static int prep(K kernel, size_t bytes) {
 
 // one draw, nothing recorded: the run of a caller that passes none
 static const EyRun kOneDraw = {1, nullptr, nullptr, nullptr, nullptr};
+// the arguments every sampler kernel but k_hmc ends with, from the draw d: temp, the Philox key, accepted, log_rate, run, C
+#define EY_DRAW_ARGS(T, d)                                                                                      \
+  (const T*)(d).temp, (d).seed, (d).iter, (d).chain_offset, (unsigned char*)(d).accepted, (T*)(d).log_rate, \
+      (d).run ? *(d).run : kOneDraw, (d).C
 
 // one kernel over C chains of nw waves: the LDS attribute, the launch, its error
 template <typename... Ps, typename... As>
@@ -1267,23 +1271,19 @@ int ey_generic_forward(ey_plan* pl, const void* theta, int64_t C, void* out, hip
 
 template <typename T, class TINY>
 static int launch_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                      const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                      uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                      hipStream_t s, const EyRun* run) {
-  return launch_row_waves<T, TINY>(pl, 3, C, s, EY_RW_KERNEL(k_hmc, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
-                                   (const T*)p0, (const T*)u, (T)step, (const T*)step_vec, L, (const T*)temp, seed, iter,
-                                   chain_offset, (int)((flags & EY_RECOMPUTE_INITIAL_GRAD) != 0), (unsigned char*)accepted,
-                                   (T*)rate, (T*)hcur, (T*)hprop, run ? run->n_iters : 1, run ? (T*)run->samples : nullptr,
-                                   run ? (T*)run->targets : nullptr, run ? (unsigned char*)run->accepted : nullptr,
-                                   run ? run->accept_count : nullptr, C);
+                      const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop) {
+  const EyRun& run = d.run ? *d.run : kOneDraw;
+  return launch_row_waves<T, TINY>(pl, 3, d.C, d.s, EY_RW_KERNEL(k_hmc, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
+                                   (const T*)p0, (const T*)u, (T)step, (const T*)step_vec, L, (const T*)d.temp, d.seed,
+                                   d.iter, d.chain_offset, (int)((d.flags & EY_RECOMPUTE_INITIAL_GRAD) != 0),
+                                   (unsigned char*)d.accepted, (T*)rate, (T*)hcur, (T*)hprop, run.n_iters, (T*)run.samples,
+                                   (T*)run.targets, (unsigned char*)run.accepted, run.accept_count, d.C);
 }
 
 int ey_generic_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                   const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                   hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc, pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed,
-                          iter, chain_offset, flags, accepted, rate, hcur, hprop, s, run);
+                   const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop) {
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc, pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur,
+                          hprop);
 }
 
 template <typename T, class TINY>
@@ -1300,35 +1300,28 @@ int ey_generic_leapfrog(ey_plan* pl, void* theta, void* p, double step, const vo
 
 template <typename T, class TINY>
 static int launch_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                       const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                       const void* step_vec, const EyDraw& d) {
   // scale = np.sqrt(step) on the python float, then cast to the model dtype (mala.py:39)
-  return launch_row_waves<T, TINY>(pl, 4, C, s, EY_RW_KERNEL(k_mala, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
-                                   (const T*)z, (const T*)u, (T)step, (T)sqrt(step), (const T*)step_vec, (const T*)temp, seed,
-                                   iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
+  return launch_row_waves<T, TINY>(pl, 4, d.C, d.s, EY_RW_KERNEL(k_mala, T, TINY), pl->m, (T*)theta, (T*)target, (T*)grad,
+                                   (const T*)z, (const T*)u, (T)step, (T)sqrt(step), (const T*)step_vec,
+                                   EY_DRAW_ARGS(T, d));
 }
 
 int ey_generic_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                    const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                    uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_mala, pl, theta, target, grad, z, u, step, step_vec, temp, C, seed, iter,
-                          chain_offset, accepted, log_rate, s, run);
+                    const void* step_vec, const EyDraw& d) {
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mala, pl, theta, target, grad, z, u, step, step_vec, d);
 }
 
 template <typename T, class TINY>
 static int launch_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                     const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                     void* log_rate, hipStream_t s, const EyRun* run) {
-  return launch_row_waves<T, TINY>(pl, 2, C, s, EY_RW_KERNEL(k_mh, T, TINY), pl->m, (T*)theta, (T*)target, (const T*)z,
-                                   (const T*)u, (const T*)scale, (const T*)temp, seed, iter, chain_offset,
-                                   (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
+                     const EyDraw& d) {
+  return launch_row_waves<T, TINY>(pl, 2, d.C, d.s, EY_RW_KERNEL(k_mh, T, TINY), pl->m, (T*)theta, (T*)target, (const T*)z,
+                                   (const T*)u, (const T*)scale, EY_DRAW_ARGS(T, d));
 }
 
 int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                  const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                  void* log_rate, hipStream_t s, const EyRun* run) {
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh, pl, theta, target, z, u, scale, temp, C, seed, iter, chain_offset,
-                          accepted, log_rate, s, run);
+                  const EyDraw& d) {
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh, pl, theta, target, z, u, scale, d);
 }
 
 // ----------------------------------------------------------------------------------------------- robust adaptive Metropolis
@@ -1511,11 +1504,9 @@ static int tril_limits(const ey_plan* pl, const std::string& name, const std::st
 
 template <typename T, class TINY>
 static int launch_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a,
-                      double g, uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                      uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  return launch(k_ram<T, TINY>, C, 1, ey_generic_ram_lds(pl), s, pl->m, (T*)theta, (T*)target, (T*)chol, (const T*)z,
-                (const T*)u, a, g, n, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
-                run ? *run : kOneDraw, C);
+                      double g, uint64_t n, const EyDraw& d) {
+  return launch(k_ram<T, TINY>, d.C, 1, ey_generic_ram_lds(pl), d.s, pl->m, (T*)theta, (T*)target, (T*)chol, (const T*)z,
+                (const T*)u, a, g, n, EY_DRAW_ARGS(T, d));
 }
 
 size_t ey_generic_ram_lds(const ey_plan* pl) {
@@ -1524,11 +1515,9 @@ size_t ey_generic_ram_lds(const ey_plan* pl) {
 }
 
 int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a, double g,
-                   uint64_t n, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                   void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                   uint64_t n, const EyDraw& d) {
   if (int rc = tril_limits(pl, "RAM", "the factor", "the factor", ey_generic_ram_lds(pl))) return rc;
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_ram, pl, theta, target, chol, z, u, a, g, n, temp, C, seed, iter,
-                          chain_offset, accepted, log_rate, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_ram, pl, theta, target, chol, z, u, a, g, n, d);
 }
 
 // ----------------------------------------------------------------------------------------------- MH with a fixed factor
@@ -1592,11 +1581,9 @@ __global__ void __launch_bounds__(WAVE) k_mh_tril(EyModel m, T* theta, T* target
 
 template <typename T, class TINY>
 static int launch_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
-                          const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                          uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  return launch(k_mh_tril<T, TINY>, C, 1, ey_generic_mh_tril_lds(pl), s, pl->m, (T*)theta, (T*)target, (const T*)tril, G,
-                (const int*)tril_index, (const T*)z, (const T*)u, (const T*)temp, seed, iter, chain_offset,
-                (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
+                          const void* z, const void* u, const EyDraw& d) {
+  return launch(k_mh_tril<T, TINY>, d.C, 1, ey_generic_mh_tril_lds(pl), d.s, pl->m, (T*)theta, (T*)target, (const T*)tril,
+                G, (const int*)tril_index, (const T*)z, (const T*)u, EY_DRAW_ARGS(T, d));
 }
 
 size_t ey_generic_mh_tril_lds(const ey_plan* pl) {
@@ -1605,11 +1592,9 @@ size_t ey_generic_mh_tril_lds(const ey_plan* pl) {
 }
 
 int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
-                       const void* z, const void* u, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                       uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                       const void* z, const void* u, const EyDraw& d) {
   if (int rc = tril_limits(pl, "MH with a factor", "the factor", "the factor", ey_generic_mh_tril_lds(pl))) return rc;
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, temp, C, seed,
-                          iter, chain_offset, accepted, log_rate, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, d);
 }
 
 // ----------------------------------------------------------------------------------------------- MALA with a fixed factor
@@ -1732,11 +1717,10 @@ __global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* targ
 template <typename T, class TINY>
 static int launch_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                             const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
-                            const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                            void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
-  return launch(k_mala_tril<T, TINY>, C, 1, ey_generic_mala_tril_lds(pl), s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                            const EyDraw& d) {
+  return launch(k_mala_tril<T, TINY>, d.C, 1, ey_generic_mala_tril_lds(pl), d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
                 (const T*)tril, G, (const int*)tril_index, (const T*)z, (const T*)u, (T)step, (const T*)step_vec,
-                (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
+                EY_DRAW_ARGS(T, d));
 }
 
 size_t ey_generic_mala_tril_lds(const ey_plan* pl) {
@@ -1746,11 +1730,10 @@ size_t ey_generic_mala_tril_lds(const ey_plan* pl) {
 
 int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
-                         const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                         void* log_rate, hipStream_t s, const EyRun* run) {
+                         const EyDraw& d) {
   if (int rc = tril_limits(pl, "MALA with a factor", "the factor", "the factor", ey_generic_mala_tril_lds(pl))) return rc;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step,
-                          step_vec, temp, C, seed, iter, chain_offset, accepted, log_rate, s, run);
+                          step_vec, d);
 }
 
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
@@ -1852,12 +1835,11 @@ __global__ void __launch_bounds__(WAVE) k_gibbs(EyModel m, T* theta, T* target, 
 
 template <typename T, class TINY>
 static int launch_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
-                        bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                        void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run) {
-  return launch(k_gibbs<T, TINY>, C, 1, ey_generic_gibbs_lds(pl, tb), s, pl->m, (T*)theta, (T*)target, (const T*)z,
+                        const EyDraw& d, double* mom_acc) {
+  return launch(k_gibbs<T, TINY>, d.C, 1, ey_generic_gibbs_lds(pl, tb), d.s, pl->m, (T*)theta, (T*)target, (const T*)z,
                 (const T*)u, (const int*)tb->d_off, (const int*)tb->d_idx, (const T*)tb->d_scale, tb->S, tb->n_idx,
-                carry ? 1 : 0, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate, mom_acc,
-                run ? *run : kOneDraw, C);
+                (d.flags & EY_GIBBS_CARRY) ? 1 : 0, (const T*)d.temp, d.seed, d.iter, d.chain_offset,
+                (unsigned char*)d.accepted, (T*)d.log_rate, mom_acc, d.run ? *d.run : kOneDraw, d.C);
 }
 
 size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb) {
@@ -1866,15 +1848,13 @@ size_t ey_generic_gibbs_lds(const ey_plan* pl, const ey_gibbs_table* tb) {
 }
 
 int ey_generic_gibbs(ey_plan* pl, const ey_gibbs_table* tb, void* theta, void* target, const void* z, const void* u,
-                     bool carry, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
-                     void* accepted, void* log_rate, double* mom_acc, hipStream_t s, const EyRun* run) {
+                     const EyDraw& d, double* mom_acc) {
   if (ey_generic_gibbs_lds(pl, tb) > 160 * 1024)
     EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the model's evaluation image and the block table (" +
                                     std::to_string(ey_generic_gibbs_lds(pl, tb)) +
                                     " bytes) do not fit the 160 KiB LDS of a CU");
   if (pl->m.kind != EY_KIND_MLP) EY_FAIL(EY_ERR_UNSUPPORTED, "Gibbs: the blocks are the nodes of an MLP; this plan has none");
-  return EY_TINY_DISPATCH(tiny_dispatch_mlp, launch_gibbs, pl, tb, theta, target, z, u, carry, temp, C, seed, iter,
-                          chain_offset, accepted, log_rate, mom_acc, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch_mlp, launch_gibbs, pl, tb, theta, target, z, u, d, mom_acc);
 }
 
 // ----------------------------------------------------------------------------------------------- softabs, one wave
@@ -2290,20 +2270,14 @@ __global__ void __launch_bounds__(WAVE) k_am(EyModel m, T* theta, T* target, EyA
 }
 
 template <typename T, class TINY>
-static int launch_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
-                     uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s,
-                     const EyRun* run) {
-  return launch(k_am<T, TINY>, C, 1, ey_generic_am_lds(pl), s, pl->m, (T*)theta, (T*)target, am, (const T*)temp, seed, iter,
-                chain_offset, (unsigned char*)accepted, (T*)log_rate, run ? *run : kOneDraw, C);
+static int launch_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d) {
+  return launch(k_am<T, TINY>, d.C, 1, ey_generic_am_lds(pl), d.s, pl->m, (T*)theta, (T*)target, am, EY_DRAW_ARGS(T, d));
 }
 
 template <typename T, class TINY>
-static int launch_am_softabs(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C,
-                             uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate,
-                             hipStream_t s, const EyRun* run) {
-  return launch(k_am<T, TINY, EY_AM_SOFTABS>, C, 1, ey_generic_am_lds(pl, EY_AM_SOFTABS), s, pl->m, (T*)theta, (T*)target,
-                am, (const T*)temp, seed, iter, chain_offset, (unsigned char*)accepted, (T*)log_rate,
-                run ? *run : kOneDraw, C);
+static int launch_am_softabs(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d) {
+  return launch(k_am<T, TINY, EY_AM_SOFTABS>, d.C, 1, ey_generic_am_lds(pl, EY_AM_SOFTABS), d.s, pl->m, (T*)theta,
+                (T*)target, am, EY_DRAW_ARGS(T, d));
 }
 
 size_t ey_generic_am_lds(const ey_plan* pl, int transform) {
@@ -2316,20 +2290,16 @@ size_t ey_generic_am_lds(const ey_plan* pl, int transform) {
   return vectors + am_extra_bytes(pl->m.P, esz) + std::max(eval_scratch, softabs_work_bytes(pl->m.P));
 }
 
-int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const void* temp, int64_t C, uint64_t seed,
-                  uint64_t iter, uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run,
-                  int transform) {
+int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, int transform) {
   if (transform == EY_AM_SOFTABS) {
     if (int rc = tril_limits(pl, "AM with softabs", "the covariance",
                              "the two covariance triangles, the f64 work matrix of softabs",
                              ey_generic_am_lds(pl, EY_AM_SOFTABS)))
       return rc;
-    return EY_TINY_DISPATCH(tiny_dispatch, launch_am_softabs, pl, theta, target, am, temp, C, seed, iter, chain_offset,
-                            accepted, log_rate, s, run);
+    return EY_TINY_DISPATCH(tiny_dispatch, launch_am_softabs, pl, theta, target, am, d);
   }
   if (int rc = tril_limits(pl, "AM", "the covariance", "the two covariance triangles", ey_generic_am_lds(pl))) return rc;
-  return EY_TINY_DISPATCH(tiny_dispatch, launch_am, pl, theta, target, am, temp, C, seed, iter, chain_offset, accepted,
-                          log_rate, s, run);
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_am, pl, theta, target, am, d);
 }
 
 bool ey_generic_am_softabs_fits(const ey_plan* pl) {

@@ -2540,9 +2540,9 @@ int ey_large_log_target(ey_plan* pl, const void* theta, const void* temp, int64_
 
 template <class T>
 static int large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                 const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                 uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                 hipStream_t s) {
+                 const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop) {
+  const int64_t C = d.C;
+  hipStream_t s = d.s;
   const EyModel& m = pl->m;
   const int P = m.P;
   const int cc = chunk_size(pl, C);
@@ -2576,12 +2576,13 @@ static int large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const v
     T* th_c = (T*)theta + c0 * P;
     T* g_c = (T*)grad + c0 * P;
     T* t_c = (T*)target + c0;
-    const T* temp_c = temp ? (const T*)temp + c0 : nullptr;
+    const T* temp_c = d.temp ? (const T*)d.temp + c0 : nullptr;
     const T* sv_c = step_vec ? (const T*)step_vec + c0 : nullptr;
     hipLaunchKernelGGL((k_hmc_begin<T>), dim3(n), dim3(256), 0, s, (const T*)th_c, (const T*)g_c,
-                       p0 ? (const T*)p0 + c0 * P : nullptr, thp, p, gp, P, seed, iter, chain_offset + (uint64_t)c0,
+                       p0 ? (const T*)p0 + c0 * P : nullptr, thp, p, gp, P, d.seed, d.iter,
+                       d.chain_offset + (uint64_t)c0,
                        (const T*)t_c, hc);
-    if (flags & EY_RECOMPUTE_INITIAL_GRAD) {  // hmc.py:104
+    if (d.flags & EY_RECOMPUTE_INITIAL_GRAD) {  // hmc.py:104
       if ((rc = eval_chunk<T>(pl, thp, temp_c, n, nullptr, nullptr, tprop, gp, ws, lik_tmp, s))) return rc;
     }
     const dim3 grid(nblk, n);
@@ -2605,7 +2606,7 @@ static int large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const v
     }
     hipLaunchKernelGGL((k_hmc_end<T>), dim3(n), dim3(256), 0, s, th_c, g_c, t_c, (const T*)thp, (const T*)p,
                        (const T*)gp, (const T*)tprop, (const T*)hc, u ? (const T*)u + c0 : nullptr, P,
-                       seed, iter, chain_offset + (uint64_t)c0, (unsigned char*)accepted + c0,
+                       d.seed, d.iter, d.chain_offset + (uint64_t)c0, (unsigned char*)d.accepted + c0,
                        rate ? (T*)rate + c0 : nullptr, hcur ? (T*)hcur + c0 : nullptr,
                        hprop ? (T*)hprop + c0 : nullptr);
   }
@@ -2613,10 +2614,8 @@ static int large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const v
   return EY_OK;
 }
 int ey_large_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                 const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                 uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                 hipStream_t s) {
-  return pl->dtype == EY_F32 ? large_hmc<float>(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags, accepted, rate, hcur, hprop, s) : large_hmc<double>(pl, theta, target, grad, p0, u, step, step_vec, L, temp, C, seed, iter, chain_offset, flags, accepted, rate, hcur, hprop, s);
+                 const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop) {
+  return pl->dtype == EY_F32 ? large_hmc<float>(pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur, hprop) : large_hmc<double>(pl, theta, target, grad, p0, u, step, step_vec, L, d, rate, hcur, hprop);
 }
 
 // ----------------------------------------------------------------------------------------------- MALA / MH / leapfrog
@@ -2701,8 +2700,9 @@ __global__ void __launch_bounds__(256) k_negate(T* p, long n) {
 // One MALA.draw (grad != null) or MetropolisHastings.draw (scale != null) for C chains
 template <class T>
 static int large_mala_mh(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                     const void* step_vec, const void* scale, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                     uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s) {
+                     const void* step_vec, const void* scale, const EyDraw& d) {
+  const int64_t C = d.C;
+  hipStream_t s = d.s;
   const EyModel& m = pl->m;
   const int P = m.P;
   const bool mala = grad != nullptr;
@@ -2721,26 +2721,25 @@ static int large_mala_mh(ey_plan* pl, void* theta, void* target, void* grad, con
     const int n = (int)((C - c0) < cc ? (C - c0) : cc);
     T* th_c = (T*)theta + c0 * P;
     T* g_c = mala ? (T*)grad + c0 * P : nullptr;
-    const T* temp_c = temp ? (const T*)temp + c0 : nullptr;
+    const T* temp_c = d.temp ? (const T*)d.temp + c0 : nullptr;
     const T* sv_c = step_vec ? (const T*)step_vec + c0 : nullptr;
     hipLaunchKernelGGL((k_propose<T>), dim3(n), dim3(256), 0, s, (const T*)th_c, (const T*)g_c,
                        z ? (const T*)z + c0 * P : nullptr, (const T*)scale, prop, P, (T)step, sv_c,
-                       sqrt_step, seed, iter, chain_offset + (uint64_t)c0);
+                       sqrt_step, d.seed, d.iter, d.chain_offset + (uint64_t)c0);
     if ((rc = eval_chunk<T>(pl, prop, temp_c, n, nullptr, nullptr, tprop, mala ? gprop : nullptr, ws, lik_tmp, s)))
       return rc;
     hipLaunchKernelGGL((k_mh_finish<T>), dim3(n), dim3(256), 0, s, th_c, g_c, (T*)target + c0, (const T*)prop,
                        mala ? (const T*)gprop : nullptr, (const T*)tprop,
-                       u ? (const T*)u + c0 : nullptr, P, (T)step, sv_c, sqrt_step, seed, iter,
-                       chain_offset + (uint64_t)c0, (unsigned char*)accepted + c0,
-                       log_rate ? (T*)log_rate + c0 : nullptr);
+                       u ? (const T*)u + c0 : nullptr, P, (T)step, sv_c, sqrt_step, d.seed, d.iter,
+                       d.chain_offset + (uint64_t)c0, (unsigned char*)d.accepted + c0,
+                       d.log_rate ? (T*)d.log_rate + c0 : nullptr);
   }
   EY_HIP(hipGetLastError());
   return EY_OK;
 }
 int ey_large_mala_mh(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                     const void* step_vec, const void* scale, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                     uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s) {
-  return pl->dtype == EY_F32 ? large_mala_mh<float>(pl, theta, target, grad, z, u, step, step_vec, scale, temp, C, seed, iter, chain_offset, accepted, log_rate, s) : large_mala_mh<double>(pl, theta, target, grad, z, u, step, step_vec, scale, temp, C, seed, iter, chain_offset, accepted, log_rate, s);
+                     const void* step_vec, const void* scale, const EyDraw& d) {
+  return pl->dtype == EY_F32 ? large_mala_mh<float>(pl, theta, target, grad, z, u, step, step_vec, scale, d) : large_mala_mh<double>(pl, theta, target, grad, z, u, step, step_vec, scale, d);
 }
 
 // HMC.leapfrog (hmc.py:100-124) as the reference runs it: L steps, L+1 gradient evaluations, momentum negated at the end

@@ -2026,7 +2026,11 @@ static int mf_launch(ey_plan* pl, MfArgs& a, hipStream_t s) {
   return mf_launch_v<MODE, 8, 0>(a, pl->n_cu, s);
 }
 
-static void mf_set_run(MfArgs& a, const EyRun* run) {
+// what every sampler mode takes of the draw: the batch, the Philox key, the accept flags and the records of a run
+static void mf_set_draw(MfArgs& a, const EyDraw& d) {
+  a.C = d.C; a.temp = (const float*)d.temp; a.seed = d.seed; a.iter = d.iter; a.chain_offset = d.chain_offset;
+  a.accepted = (unsigned char*)d.accepted;
+  const EyRun* run = d.run;
   a.n_iters = 1;
   if (run) {
     a.n_iters = run->n_iters;
@@ -2038,9 +2042,7 @@ static void mf_set_run(MfArgs& a, const EyRun* run) {
 }
 
 int ey_mfma32_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void* p0, const void* u, double step,
-                  const void* step_vec, int L, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                  uint64_t chain_offset, uint32_t flags, void* accepted, void* rate, void* hcur, void* hprop,
-                  hipStream_t s, const EyRun* run, const EyDA* da) {
+                  const void* step_vec, int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const EyDA* da) {
   MfArgs a = {};
   if (da && da->state) {
     a.da_state = da->state; a.da_tab = da->table; a.da_step = (float*)da->step; a.da_n = da->n;
@@ -2048,37 +2050,31 @@ int ey_mfma32_hmc(ey_plan* pl, void* theta, void* target, void* grad, const void
   }
   // while a dual averaging is attached its step vector is THE step, also once its table is used up (include/eeyore_amd.h)
   if (da && da->step) step_vec = da->step;  // the kernel reads each iteration's step where the previous one's update left it
-  a.C = C; a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)grad;
+  a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)grad;
   a.p0 = (const float*)p0; a.u = (const float*)u; a.step = (float)step; a.step_vec = (const float*)step_vec;
-  a.L = L; a.temp = (const float*)temp; a.seed = seed; a.iter = iter; a.chain_offset = chain_offset;
-  a.recompute = (flags & EY_RECOMPUTE_INITIAL_GRAD) ? 1 : 0;
-  a.accepted = (unsigned char*)accepted; a.rate = (float*)rate; a.hcur = (float*)hcur; a.hprop = (float*)hprop;
-  mf_set_run(a, run);
-  return mf_finish(pl, a, mf_launch<MODE_HMC>(pl, a, s), s);
+  a.L = L; a.recompute = (d.flags & EY_RECOMPUTE_INITIAL_GRAD) ? 1 : 0;
+  a.rate = (float*)rate; a.hcur = (float*)hcur; a.hprop = (float*)hprop;
+  mf_set_draw(a, d);
+  return mf_finish(pl, a, mf_launch<MODE_HMC>(pl, a, d.s), d.s);
 }
 
 int ey_mfma32_mala(ey_plan* pl, void* theta, void* target, void* grad, const void* z, const void* u, double step,
-                   const void* step_vec, const void* temp, int64_t C, uint64_t seed, uint64_t iter,
-                   uint64_t chain_offset, void* accepted, void* log_rate, hipStream_t s, const EyRun* run) {
+                   const void* step_vec, const EyDraw& d) {
   MfArgs a = {};
-  a.C = C; a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)grad;
+  a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)grad;
   a.p0 = (const float*)z; a.u = (const float*)u; a.step = (float)step; a.sqrt_step = (float)sqrt(step);
-  a.step_vec = (const float*)step_vec; a.temp = (const float*)temp; a.seed = seed; a.iter = iter;
-  a.chain_offset = chain_offset; a.accepted = (unsigned char*)accepted; a.rate = (float*)log_rate;
-  mf_set_run(a, run);
-  return mf_finish(pl, a, mf_launch<MODE_MALA>(pl, a, s), s);
+  a.step_vec = (const float*)step_vec; a.rate = (float*)d.log_rate;
+  mf_set_draw(a, d);
+  return mf_finish(pl, a, mf_launch<MODE_MALA>(pl, a, d.s), d.s);
 }
 
 int ey_mfma32_mh(ey_plan* pl, void* theta, void* target, const void* z, const void* u, const void* scale,
-                 const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, void* accepted,
-                 void* log_rate, hipStream_t s, const EyRun* run) {
+                 const EyDraw& d) {
   MfArgs a = {};
-  a.C = C; a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)theta;  // grad unused by MH
-  a.p0 = (const float*)z; a.u = (const float*)u; a.scale = (const float*)scale; a.temp = (const float*)temp;
-  a.seed = seed; a.iter = iter; a.chain_offset = chain_offset; a.accepted = (unsigned char*)accepted;
-  a.rate = (float*)log_rate;
-  mf_set_run(a, run);
-  return mf_finish(pl, a, mf_launch<MODE_MH>(pl, a, s), s);
+  a.theta = (float*)theta; a.target = (float*)target; a.grad = (float*)theta;  // grad unused by MH
+  a.p0 = (const float*)z; a.u = (const float*)u; a.scale = (const float*)scale; a.rate = (float*)d.log_rate;
+  mf_set_draw(a, d);
+  return mf_finish(pl, a, mf_launch<MODE_MH>(pl, a, d.s), d.s);
 }
 
 int ey_mfma32_log_target_grad(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* target, void* grad,

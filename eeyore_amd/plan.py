@@ -399,19 +399,58 @@ class Plan:
             for _ in range(times):
                 self._moments[3]()
 
+    # ------------------------------------------------------------------ samplers
+    def _want(self, name, t, shape, dtype, msg=None):
+        """``t`` is a contiguous tensor of that shape and dtype on the plan's device, or ValueError (``msg`` where a
+        caller words it its own way)."""
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(msg or f"{name} must be a contiguous {dtype} tensor of shape {shape} on the plan's device")
+
+    def _records(self, n_iters, C, samples, targets, accepted_rec, accept_count, each=()):
+        for name, t, shape, dt in (("samples", samples, (n_iters, C, self.P), self.dtype),
+                                   ("targets", targets, (n_iters, C), self.dtype),
+                                   ("accepted_rec", accepted_rec, (n_iters, C) + each, torch.uint8),
+                                   ("accept_count", accept_count, (C,) + each, torch.int32)):
+            if t is not None:
+                self._want(name, t, shape, dt)
+
+    def _sample(self, fn, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=None, records=None, each=(),
+                tail=None):
+        """One call of the sampler entry point ``fn``.  ``lead``: its own arguments between the plan and
+        ``temp``; ``out``: the caller's dict or None (then accepted and, for a step, log_rate, of shape [C]);
+        ``n_iters`` and ``records`` (samples, targets, accepted_rec, accept_count) make it a run; ``tail``: what the
+        entry point takes between accepted and the stream (None: a step's log_rate, nothing for a run).  ``lead`` and
+        ``tail`` hold device pointers (``L.ptr``): a caller that converts an argument (``_opt``) keeps the result in a
+        local, alive until the call has queued its work.  ``each``: the trailing shape of Gibbs's per-block records."""
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8))
+            if n_iters is None:
+                out["log_rate"] = self.empty(C)
+        temp = self._opt(temp, C)
+        if n_iters is None:
+            rc = fn(self.handle, *lead, L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
+                    L.ptr(out["accepted"]), *(tail or (L.ptr(out["log_rate"]),)), _stream(self.device))
+        else:
+            n_iters = int(n_iters)
+            self._records(n_iters, C, *records, each)
+            rc = fn(self.handle, *lead, L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
+                    *[L.ptr(r) for r in records], L.ptr(out["accepted"]), *(tail or ()), _stream(self.device))
+        if rc:  # (L.check and _stepped return at once for most draws; not calling them is 0.2 us of every sampler call)
+            L.check(rc, fn.__name__)
+        if self._moments is not None:
+            self._stepped(n_iters or 1)
+        return out
+
     def hmc_step(self, theta, target, grad, step, num_steps, p0=None, u=None, step_vec=None, temp=None, seed=0, it=0,
                  chain_offset=0, flags=0, out=None):
         C = self._theta(theta)
         if out is None:
             out = dict(accepted=self.empty(C, dtype=torch.uint8), rate=self.empty(C), h_cur=self.empty(C),
                        h_prop=self.empty(C))
-        temp, step_vec, u = self._opt(temp, C), self._opt(step_vec, C), self._opt(u, C)
-        L.check(L.lib().ey_hmc_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(p0), L.ptr(u),
-                                    float(step), L.ptr(step_vec), int(num_steps), L.ptr(temp), C, int(seed), int(it),
-                                    int(chain_offset), int(flags), L.ptr(out["accepted"]), L.ptr(out["rate"]),
-                                    L.ptr(out["h_cur"]), L.ptr(out["h_prop"]), _stream(self.device)), "ey_hmc_step")
-        self._stepped()
-        return out
+        u, step_vec = self._opt(u, C), self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(p0), L.ptr(u), float(step), L.ptr(step_vec), int(num_steps))
+        return self._sample(L.lib().ey_hmc_step, C, lead, temp, seed, it, chain_offset, flags, out,
+                            tail=(L.ptr(out["rate"]), L.ptr(out["h_cur"]), L.ptr(out["h_prop"])))
 
     def hmc_run(self, theta, target, grad, step, num_steps, n_iters, step_vec=None, temp=None, seed=0, it=0,
                 chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
@@ -420,59 +459,28 @@ class Plan:
         state after each iteration: ``samples`` [n_iters, C, P], ``targets`` [n_iters, C], ``accepted_rec`` [n_iters, C]
         uint8 (contiguous views, e.g. slices of a ChainBuffer's storage); ``accept_count`` [C] int32 is incremented."""
         C = self._theta(theta)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
-        temp, step_vec = self._opt(temp, C), self._opt(step_vec, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_hmc_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), float(step), L.ptr(step_vec),
-                                   int(num_steps), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
-                                   n_iters, L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
-                                   L.ptr(out["accepted"]), _stream(self.device)), "ey_hmc_run")
-        self._stepped(n_iters)
-        return out
-
-    def _records(self, n_iters, C, samples, targets, accepted_rec, accept_count):
-        for name, t, shape, dt in (("samples", samples, (n_iters, C, self.P), self.dtype),
-                                   ("targets", targets, (n_iters, C), self.dtype),
-                                   ("accepted_rec", accepted_rec, (n_iters, C), torch.uint8),
-                                   ("accept_count", accept_count, (C,), torch.int32)):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
-                                  or t.device != self.device):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the plan's device")
+        step_vec = self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), float(step), L.ptr(step_vec), int(num_steps))
+        return self._sample(L.lib().ey_hmc_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def mala_run(self, theta, target, grad, step, n_iters, step_vec=None, temp=None, seed=0, it=0, chain_offset=0,
                  flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
         """``n_iters`` MALA iterations of every chain in one launch (ey_mala_run); records as in ``hmc_run``."""
         C = self._theta(theta)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
-        temp, step_vec = self._opt(temp, C), self._opt(step_vec, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_mala_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), float(step), L.ptr(step_vec),
-                                    L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
-                                    L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
-                                    L.ptr(out["accepted"]), _stream(self.device)), "ey_mala_run")
-        self._stepped(n_iters)
-        return out
+        step_vec = self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), float(step), L.ptr(step_vec))
+        return self._sample(L.lib().ey_mala_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def mh_run(self, theta, target, scale, n_iters, temp=None, seed=0, it=0, chain_offset=0, flags=0, samples=None,
                targets=None, accepted_rec=None, accept_count=None, out=None):
         """``n_iters`` random-walk MH iterations of every chain in one launch (ey_mh_run); records as in ``hmc_run``."""
         C = self._theta(theta)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
         scale = self._prep(torch.broadcast_to(torch.as_tensor(scale, dtype=self.dtype, device=self.device), (self.P,)))
-        temp = self._opt(temp, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_mh_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(scale), L.ptr(temp), C, int(seed),
-                                  int(it), int(chain_offset), int(flags), n_iters, L.ptr(samples), L.ptr(targets),
-                                  L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
-                                  _stream(self.device)), "ey_mh_run")
-        self._stepped(n_iters)
-        return out
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(scale))
+        return self._sample(L.lib().ey_mh_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def leapfrog(self, theta, p, step, num_steps, step_vec=None, temp=None):
         """HMC.leapfrog (hmc.py:100-124) in place on theta [C,P], p [C,P]; returns (target [C], grad [C,P])."""
@@ -488,27 +496,16 @@ class Plan:
     def mala_step(self, theta, target, grad, step, z=None, u=None, step_vec=None, temp=None, seed=0, it=0,
                   chain_offset=0, flags=0, out=None):
         C = self._theta(theta)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
-        temp, step_vec, u = self._opt(temp, C), self._opt(step_vec, C), self._opt(u, C)
-        L.check(L.lib().ey_mala_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(z), L.ptr(u),
-                                     float(step), L.ptr(step_vec), L.ptr(temp), C, int(seed), int(it),
-                                     int(chain_offset), int(flags), L.ptr(out["accepted"]), L.ptr(out["log_rate"]),
-                                     _stream(self.device)), "ey_mala_step")
-        self._stepped()
-        return out
+        u, step_vec = self._opt(u, C), self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(z), L.ptr(u), float(step), L.ptr(step_vec))
+        return self._sample(L.lib().ey_mala_step, C, lead, temp, seed, it, chain_offset, flags, out)
 
     def mh_step(self, theta, target, scale, z=None, u=None, temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
         C = self._theta(theta)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
         scale = self._prep(torch.broadcast_to(torch.as_tensor(scale, dtype=self.dtype, device=self.device), (self.P,)))
-        temp, u = self._opt(temp, C), self._opt(u, C)
-        L.check(L.lib().ey_mh_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(z), L.ptr(u), L.ptr(scale),
-                                   L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
-                                   L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)), "ey_mh_step")
-        self._stepped()
-        return out
+        u = self._opt(u, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(z), L.ptr(u), L.ptr(scale))
+        return self._sample(L.lib().ey_mh_step, C, lead, temp, seed, it, chain_offset, flags, out)
 
     def _tril(self, tril, index, C):
         """(G, index) of a proposal factor ``tril`` ([P, P] or [G, P, P]) for C chains, checked: without ``index`` G is 1
@@ -540,32 +537,18 @@ class Plan:
         naming each chain's factor.  Only the lower triangle is read."""
         C = self._theta(theta)
         G, index = self._tril(tril, index, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
-        temp, u = self._opt(temp, C), self._opt(u, C)
-        L.check(L.lib().ey_mh_tril_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index), L.ptr(z),
-                                        L.ptr(u), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
-                                        L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)),
-                "ey_mh_tril_step")
-        self._stepped()
-        return out
+        u = self._opt(u, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index), L.ptr(z), L.ptr(u))
+        return self._sample(L.lib().ey_mh_tril_step, C, lead, temp, seed, it, chain_offset, flags, out)
 
     def mh_tril_run(self, theta, target, tril, n_iters, index=None, temp=None, seed=0, it=0, chain_offset=0, flags=0,
                     samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
         """``n_iters`` iterations of ``mh_tril_step`` in one launch (ey_mh_tril_run); records as in ``hmc_run``."""
         C = self._theta(theta)
         G, index = self._tril(tril, index, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
-        temp = self._opt(temp, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_mh_tril_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index),
-                                       L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
-                                       L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
-                                       L.ptr(out["accepted"]), _stream(self.device)), "ey_mh_tril_run")
-        self._stepped(n_iters)
-        return out
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(tril), G, L.ptr(index))
+        return self._sample(L.lib().ey_mh_tril_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def mala_tril_step(self, theta, target, grad, step, tril, index=None, z=None, u=None, step_vec=None, temp=None, seed=0,
                        it=0, chain_offset=0, flags=0, out=None):
@@ -573,38 +556,25 @@ class Plan:
         ``index`` as in ``mh_tril_step``, the rest as in ``mala_step``.  Only the lower triangle is read."""
         C = self._theta(theta)
         G, index = self._tril(tril, index, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
-        temp, step_vec, u = self._opt(temp, C), self._opt(step_vec, C), self._opt(u, C)
-        L.check(L.lib().ey_mala_tril_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G,
-                                          L.ptr(index), L.ptr(z), L.ptr(u), float(step), L.ptr(step_vec), L.ptr(temp), C,
-                                          int(seed), int(it), int(chain_offset), int(flags), L.ptr(out["accepted"]),
-                                          L.ptr(out["log_rate"]), _stream(self.device)), "ey_mala_tril_step")
-        self._stepped()
-        return out
+        u, step_vec = self._opt(u, C), self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G, L.ptr(index), L.ptr(z), L.ptr(u), float(step),
+                L.ptr(step_vec))
+        return self._sample(L.lib().ey_mala_tril_step, C, lead, temp, seed, it, chain_offset, flags, out)
 
     def mala_tril_run(self, theta, target, grad, step, tril, n_iters, index=None, step_vec=None, temp=None, seed=0, it=0,
                       chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
         """``n_iters`` iterations of ``mala_tril_step`` in one launch (ey_mala_tril_run); records as in ``hmc_run``."""
         C = self._theta(theta)
         G, index = self._tril(tril, index, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
-        temp, step_vec = self._opt(temp, C), self._opt(step_vec, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_mala_tril_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G,
-                                         L.ptr(index), float(step), L.ptr(step_vec), L.ptr(temp), C, int(seed), int(it),
-                                         int(chain_offset), int(flags), n_iters, L.ptr(samples), L.ptr(targets),
-                                         L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
-                                         _stream(self.device)), "ey_mala_tril_run")
-        self._stepped(n_iters)
-        return out
+        step_vec = self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(tril), G, L.ptr(index), float(step), L.ptr(step_vec))
+        return self._sample(L.lib().ey_mala_tril_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def _chol(self, chol, C):
-        if (chol.device != self.device or chol.dtype != self.dtype or not chol.is_contiguous()
-                or tuple(chol.shape) != (C, self.P, self.P)):
-            raise ValueError(f"chol must be a contiguous [{C}, {self.P}, {self.P}] tensor of the plan's dtype on its device")
+        P = self.P
+        self._want("chol", chol, (C, P, P), self.dtype,
+                   f"chol must be a contiguous [{C}, {P}, {P}] tensor of the plan's dtype on its device")
 
     def ram_step(self, theta, target, chol, n, a=0.234, g=0.7, z=None, u=None, temp=None, seed=0, it=0, chain_offset=0,
                  flags=0, out=None):
@@ -612,14 +582,9 @@ class Plan:
         lower-triangular factor chol [C,P,P] are updated in place; ``n`` is the adaptation index counter.idx + 1 - offset."""
         C = self._theta(theta)
         self._chol(chol, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C))
-        temp, u = self._opt(temp, C), self._opt(u, C)
-        L.check(L.lib().ey_ram_step(self.handle, L.ptr(theta), L.ptr(target), L.ptr(chol), L.ptr(z), L.ptr(u), float(a),
-                                    float(g), int(n), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags),
-                                    L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)), "ey_ram_step")
-        self._stepped()
-        return out
+        u = self._opt(u, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(chol), L.ptr(z), L.ptr(u), float(a), float(g), int(n))
+        return self._sample(L.lib().ey_ram_step, C, lead, temp, seed, it, chain_offset, flags, out)
 
     def ram_run(self, theta, target, chol, n, n_iters, a=0.234, g=0.7, temp=None, seed=0, it=0, chain_offset=0, flags=0,
                 samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
@@ -627,17 +592,9 @@ class Plan:
         records as in ``hmc_run``."""
         C = self._theta(theta)
         self._chol(chol, C)
-        if out is None:
-            out = dict(accepted=self.empty(C, dtype=torch.uint8))
-        temp = self._opt(temp, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        L.check(L.lib().ey_ram_run(self.handle, L.ptr(theta), L.ptr(target), L.ptr(chol), float(a), float(g), int(n),
-                                   L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
-                                   L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count),
-                                   L.ptr(out["accepted"]), _stream(self.device)), "ey_ram_run")
-        self._stepped(n_iters)
-        return out
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(chol), float(a), float(g), int(n))
+        return self._sample(L.lib().ey_ram_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
 
     def gibbs_table(self, blocks, scales):
         """The device block table of a Gibbs sampler on this plan (ey_gibbs_table_create): ``blocks`` is a list of S
@@ -658,19 +615,14 @@ class Plan:
         Returns accepted [C,S] uint8 and log_rate [C,S]."""
         C = self._theta(theta)
         S, carry = self._gibbs_args(table, C, mode)
+        for name, t, shape in (("z", z, (C, self.P)), ("u", u, (C, S))):
+            if t is not None:
+                self._want(name, t, shape, self.dtype,
+                           f"{name} must be a contiguous {shape} tensor of the plan's dtype on its device")
         if out is None:
             out = dict(accepted=self.empty(C, S, dtype=torch.uint8), log_rate=self.empty(C, S))
-        for name, t, shape in (("z", z, (C, self.P)), ("u", u, (C, S))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != self.dtype or not t.is_contiguous()
-                                  or t.device != self.device):
-                raise ValueError(f"{name} must be a contiguous {shape} tensor of the plan's dtype on its device")
-        temp = self._opt(temp, C)
-        L.check(L.lib().ey_gibbs_step(self.handle, table.handle, L.ptr(theta), L.ptr(target), L.ptr(z), L.ptr(u),
-                                      L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags) | carry,
-                                      L.ptr(out["accepted"]), L.ptr(out["log_rate"]), _stream(self.device)),
-                "ey_gibbs_step")
-        self._stepped()
-        return out
+        lead = (table.handle, L.ptr(theta), L.ptr(target), L.ptr(z), L.ptr(u))
+        return self._sample(L.lib().ey_gibbs_step, C, lead, temp, seed, it, chain_offset, int(flags) | carry, out)
 
     def gibbs_run(self, theta, target, table, n_iters, mode='intended', temp=None, seed=0, it=0, chain_offset=0, flags=0,
                   samples=None, targets=None, accepted_rec=None, accept_count=None, out=None):
@@ -680,20 +632,9 @@ class Plan:
         S, carry = self._gibbs_args(table, C, mode)
         if out is None:
             out = dict(accepted=self.empty(C, S, dtype=torch.uint8))
-        temp = self._opt(temp, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, None, None)
-        for name, t, shape, dt in (("accepted_rec", accepted_rec, (n_iters, C, S), torch.uint8),
-                                   ("accept_count", accept_count, (C, S), torch.int32)):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
-                                  or t.device != self.device):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the plan's device")
-        L.check(L.lib().ey_gibbs_run(self.handle, table.handle, L.ptr(theta), L.ptr(target), L.ptr(temp), C, int(seed),
-                                     int(it), int(chain_offset), int(flags) | carry, n_iters, L.ptr(samples),
-                                     L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
-                                     _stream(self.device)), "ey_gibbs_run")
-        self._stepped(n_iters)
-        return out
+        lead = (table.handle, L.ptr(theta), L.ptr(target))
+        return self._sample(L.lib().ey_gibbs_run, C, lead, temp, seed, it, chain_offset, int(flags) | carry, out,
+                            n_iters=n_iters, records=(samples, targets, accepted_rec, accept_count), each=(S,))
 
     def _am_state(self, C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns):
         P = self.P
@@ -701,13 +642,22 @@ class Plan:
                                    ("cov_sum", cov_sum, (C, P, P), self.dtype), ("cov", cov, (C, P, P), self.dtype),
                                    ("num_accepted", num_accepted, (C,), torch.int32),
                                    ("breakdowns", breakdowns, (C,), torch.int32)):
-            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the plan's device")
-        if (cov0.dtype != self.dtype or not cov0.is_contiguous() or cov0.device != self.device
-                or tuple(cov0.shape) not in ((P, P), (C, P, P))):
-            raise ValueError(f"cov0 must be a contiguous [{P}, {P}] or [{C}, {P}, {P}] tensor of the plan's dtype on its "
-                             "device")
+            self._want(name, t, shape, dt)
+        self._want("cov0", cov0, (P, P) if cov0.dim() == 2 else (C, P, P), self.dtype,
+                   f"cov0 must be a contiguous [{P}, {P}] or [{C}, {P}, {P}] tensor of the plan's dtype on its device")
         return int(cov0.dim() == 3)
+
+    def _am(self, kind, theta, target, state, cov0, breakdowns, settings, softabs_a):
+        """(entry, C, the leading arguments, breakdowns) of ey_am_<kind> (ey_am_softabs_<kind> with ``softabs_a``, which
+        then takes the place of eps) on the checked ``state`` = (running_mean, cov_sum, cov, num_accepted)."""
+        C = self._theta(theta)
+        if breakdowns is None:
+            breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
+        per_chain = self._am_state(C, *state, cov0, breakdowns)
+        l, b, c, eps, t0, idx, offset = settings
+        lead = (L.ptr(theta), L.ptr(target), *[L.ptr(t) for t in state], L.ptr(cov0), per_chain, float(l), float(b), float(c),
+                float(eps if softabs_a is None else softabs_a), int(t0), int(idx), int(offset))
+        return ("ey_am_" if softabs_a is None else "ey_am_softabs_") + kind, C, lead, breakdowns
 
     def am_step(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, l=0.05, b=1., c=1., eps=0.,
                 t0=2, offset=0, z=None, u_mix=None, u=None, temp=None, seed=0, it=0, chain_offset=0, flags=0,
@@ -717,49 +667,29 @@ class Plan:
         theta [C,P], target [C], running_mean [C,P], cov_sum and cov [C,P,P] (lower triangles) and num_accepted [C] int32
         are updated in place; ``cov0`` is the transformed initial covariance, ``idx`` the counter index of the draw.
         ``breakdowns`` [C] int32 is incremented for a chain whose covariance could not be factorised."""
-        C = self._theta(theta)
-        if breakdowns is None:
-            breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
-        per_chain = self._am_state(C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns)
+        entry, C, lead, breakdowns = self._am("step", theta, target, (running_mean, cov_sum, cov, num_accepted), cov0,
+                                              breakdowns, (l, b, c, eps, t0, idx, offset), softabs_a)
         if out is None:
             out = dict(accepted=self.empty(C, dtype=torch.uint8), log_rate=self.empty(C),
                        branch=self.empty(C, dtype=torch.uint8))
         out["breakdowns"] = breakdowns
-        temp, u, u_mix = self._opt(temp, C), self._opt(u, C), self._opt(u_mix, C)
-        fn, who, par = ((L.lib().ey_am_step, "ey_am_step", eps) if softabs_a is None else
-                        (L.lib().ey_am_softabs_step, "ey_am_softabs_step", softabs_a))
-        L.check(fn(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum), L.ptr(cov),
-                   L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c), float(par), int(t0),
-                   int(idx), int(offset), L.ptr(z), L.ptr(u_mix), L.ptr(u), L.ptr(temp), C, int(seed), int(it),
-                   int(chain_offset), int(flags), L.ptr(out["accepted"]), L.ptr(out.get("log_rate")),
-                   L.ptr(out.get("branch")), L.ptr(breakdowns), _stream(self.device)), who)
-        self._stepped()
-        return out
+        u_mix, u = self._opt(u_mix, C), self._opt(u, C)
+        lead += (L.ptr(z), L.ptr(u_mix), L.ptr(u))
+        return self._sample(getattr(L.lib(), entry), C, lead, temp, seed, it, chain_offset, flags, out,
+                            tail=(L.ptr(out.get("log_rate")), L.ptr(out.get("branch")), L.ptr(breakdowns)))
 
     def am_run(self, theta, target, running_mean, cov_sum, cov, num_accepted, cov0, idx, n_iters, l=0.05, b=1., c=1.,
                eps=0., t0=2, offset=0, temp=None, seed=0, it=0, chain_offset=0, flags=0, breakdowns=None, samples=None,
                targets=None, accepted_rec=None, accept_count=None, out=None, softabs_a=None):
         """``n_iters`` AM iterations of every chain in one launch (ey_am_run; ey_am_softabs_run with ``softabs_a``),
         counter indices idx, idx + 1, ...; records as in ``hmc_run``."""
-        C = self._theta(theta)
-        if breakdowns is None:
-            breakdowns = torch.zeros(C, dtype=torch.int32, device=self.device)
-        per_chain = self._am_state(C, running_mean, cov_sum, cov, num_accepted, cov0, breakdowns)
+        entry, C, lead, breakdowns = self._am("run", theta, target, (running_mean, cov_sum, cov, num_accepted), cov0,
+                                              breakdowns, (l, b, c, eps, t0, idx, offset), softabs_a)
         if out is None:
             out = dict(accepted=self.empty(C, dtype=torch.uint8))
         out["breakdowns"] = breakdowns
-        temp = self._opt(temp, C)
-        n_iters = int(n_iters)
-        self._records(n_iters, C, samples, targets, accepted_rec, accept_count)
-        fn, who, par = ((L.lib().ey_am_run, "ey_am_run", eps) if softabs_a is None else
-                        (L.lib().ey_am_softabs_run, "ey_am_softabs_run", softabs_a))
-        L.check(fn(self.handle, L.ptr(theta), L.ptr(target), L.ptr(running_mean), L.ptr(cov_sum), L.ptr(cov),
-                   L.ptr(num_accepted), L.ptr(cov0), per_chain, float(l), float(b), float(c), float(par), int(t0),
-                   int(idx), int(offset), L.ptr(temp), C, int(seed), int(it), int(chain_offset), int(flags), n_iters,
-                   L.ptr(samples), L.ptr(targets), L.ptr(accepted_rec), L.ptr(accept_count), L.ptr(out["accepted"]),
-                   L.ptr(breakdowns), _stream(self.device)), who)
-        self._stepped(n_iters)
-        return out
+        return self._sample(getattr(L.lib(), entry), C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count), tail=(L.ptr(breakdowns),))
 
     def am_softabs_fits(self):
         """Whether the softabs instantiation of the AM kernel has room for this plan's model (ey_am_softabs_fits)."""
