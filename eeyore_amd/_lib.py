@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h).
+"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -98,6 +98,14 @@ SYMBOLS = {
     "ey_debug_bgemm": (_i, [_vp, _vp, _vp, _i, _i, _i] + [_i64] * 9 + [_vp, _i64, _i, _i, _vp]),
 }
 
+# ... and every symbol include/eeyore_amd_ext.h declares, the entry points added since that surface was recorded: a table of
+# its own, bound by lib() beside SYMBOLS
+EY_METRIC_DIAG, EY_METRIC_TRIL = 0, 1
+EXT_SYMBOLS = {
+    "ey_hmc_metric_step": (_i, [_vp] * 5 + [_i, _i64] + [_vp] * 3 + [_d, _vp, _i] + _DRAW + [_vp] * 5),
+    "ey_hmc_metric_run": (_i, [_vp] * 5 + [_i, _i64, _vp, _d, _vp, _i] + _RUN),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -128,7 +136,7 @@ def lib():
                 f"eeyore_amd: HIP library {LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C eeyore_amd/csrc`); there is no CPU fallback")
         L = ct.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -955,6 +955,28 @@ static int mala_tril_impl(ey_plan* pl, void* theta, void* target, void* grad, co
   return f.finish(ey_generic_mala_tril(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, d), theta);
 }
 
+// HMC with a fixed metric: one kernel of ey_generic.hip for every model, as the samplers with a factor above.  An attached
+// dual averaging is refused, not ignored: this kernel does not consume the table, and hmc_impl's callers rely on it.
+static int hmc_metric_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                           const void* metric_index, const void* v0, const void* u, double step, const void* step_vec,
+                           int L, const EyDraw& d, void* rate, void* hcur, void* hprop, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !grad || !metric || !d.accepted) return f.refuse("null argument");
+  if (form != EY_METRIC_DIAG && form != EY_METRIC_TRIL)
+    return f.refuse("form must be EY_METRIC_DIAG or EY_METRIC_TRIL");
+  if (L < 1) return f.refuse("num_steps must be >= 1");
+  EY_TRY(f.step(step, step_vec));
+  EY_TRY(f.n_iters());
+  EY_TRY(f.factors(G, metric_index));
+  if (pl->da_state)
+    return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which HMC with a metric does not consume; "
+                    "detach it and adapt on the host");
+  EY_TRY(f.ready(true));
+  return f.finish(ey_generic_hmc_metric(pl, theta, target, grad, metric, form, G, metric_index, v0, u, step, step_vec, L,
+                                        d, rate, hcur, hprop), theta);
+}
+
 static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, const char* who,
                    int transform) {
   EyCall f{pl, d, who};
@@ -1080,6 +1102,26 @@ int ey_mala_tril_run(ey_plan* pl, void* theta, void* target, void* grad, const v
   const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
   return mala_tril_impl(pl, theta, target, grad, tril, G, tril_index, nullptr, nullptr, step, step_vec, d,
                         "ey_mala_tril_run");
+}
+
+// (declared in include/eeyore_amd_ext.h)
+int ey_hmc_metric_step(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                       const void* metric_index, const void* v0, const void* u, double step, const void* step_vec, int L,
+                       const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags,
+                       void* accepted, void* accept_rate, void* H_cur, void* H_prop, void* stream) {
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, nullptr};
+  return hmc_metric_impl(pl, theta, target, grad, metric, form, G, metric_index, v0, u, step, step_vec, L, d, accept_rate,
+                         H_cur, H_prop, "ey_hmc_metric_step");
+}
+
+int ey_hmc_metric_run(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                      const void* metric_index, double step, const void* step_vec, int L, const void* temp, int64_t C,
+                      uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                      void* targets, void* accepted_rec, void* accept_count, void* accepted, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  return hmc_metric_impl(pl, theta, target, grad, metric, form, G, metric_index, nullptr, nullptr, step, step_vec, L, d,
+                         nullptr, nullptr, nullptr, "ey_hmc_metric_run");
 }
 
 int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,

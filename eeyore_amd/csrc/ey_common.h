@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <string>
 
-#include "../../include/eeyore_amd.h"
+#include "../../include/eeyore_amd_ext.h"  // includes eeyore_amd.h
 
 #define EY_MAX_LAYERS 8
 #define EY_VERSION 200  // 0.2.0
@@ -220,6 +220,11 @@ size_t ey_generic_mala_tril_lds(const ey_plan* pl);  // dynamic LDS of one chain
 int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                          const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
                          const EyDraw& d);
+// HMC with a fixed metric, EY_METRIC_DIAG or EY_METRIC_TRIL (k_hmc_metric): one wave per chain, whatever plan.kernel says
+size_t ey_generic_hmc_metric_lds(const ey_plan* pl, int form);  // dynamic LDS of one chain's workgroup
+int ey_generic_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                          const void* metric_index, const void* v0, const void* u, double step, const void* step_vec, int L,
+                          const EyDraw& d, void* rate, void* hcur, void* hprop);
 
 #define EY_AM_RIDGE 0
 #define EY_AM_SOFTABS 1

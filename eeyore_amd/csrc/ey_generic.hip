@@ -1345,10 +1345,13 @@ __host__ __device__ static size_t ram_extra_bytes(int P, size_t esz) {
 
 // ---- steps the one-wave kernels share (k_ram, k_mh_tril, k_mala_tril, k_am, k_gibbs), macros as the kernels' above
 // Lg: chain c's factor in tril [G, P, P], chosen as the comment of k_mh_tril says (G, tril_index, clamped into [0, G)).
-// DECLARES g and Lg.  Reads: T, tril, tril_index, G, c, P.
-#define EY_CHAIN_FACTOR(Lg)                                           \
-  int64_t g = G == 1 ? 0 : (tril_index ? (int64_t)tril_index[c] : c); \
-  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);                            \
+// DECLARES g and Lg.  Reads: T, tril, tril_index, G, c, P.  EY_CHAIN_INDEX is its choice alone, for a table of another
+// stride (k_hmc_metric's [G, P] scales): DECLARES g.  Reads: G, c.
+#define EY_CHAIN_INDEX(g, index)                            \
+  int64_t g = G == 1 ? 0 : ((index) ? (int64_t)(index)[c] : c); \
+  g = g < 0 ? 0 : (g > G - 1 ? G - 1 : g)
+#define EY_CHAIN_FACTOR(Lg)        \
+  EY_CHAIN_INDEX(g, tril_index);   \
   const T* Lg = tril + g * (int64_t)P * P
 
 // z of a draw into the LDS vector dst: the chain's own stream, or the caller's values.  Reads: T, z_in, rn, c, P, lane.
@@ -1383,6 +1386,31 @@ __host__ __device__ static size_t ram_extra_bytes(int P, size_t esz) {
         (acc)[r] += ((b) * (on ? s : T(0))) * zj; \
       }                                           \
     }                                             \
+  } while (0)
+
+// acc[r] += sum_i (b S[i, j]) x[i] for the packed factor S and the lane's R COLUMNS j = lane + 64 r: the transposed product
+// L^T x.  The packed order keeps a column contiguous from its diagonal down, so a lane walks its own columns.  Every lane
+// sums over i = 0, 1, ..., P - 1 in that order -- the rows above a column's diagonal enter with the factor selected to zero
+// behind an index clamped onto the diagonal -- so the trip count is wave-uniform and the order of a sum depends on
+// nothing but P.  A lane without a column (j >= P) takes column P - 1 and repeats its owner's work: the same inputs, hence
+// the same bits (EY_LANE_PASS's rule).  x is read as a broadcast.  Reads: T, P, lane.
+#define EY_TRIL_TSWEEP(S, x, R, b, acc)                                         \
+  do {                                                                          \
+    const int ey_j0_ = lane < P ? lane : P - 1;                                 \
+    const int ey_j1_ = lane + WAVE < P ? lane + WAVE : P - 1;                   \
+    const T* ey_c0_ = (S) + ram_col(ey_j0_, P) - ey_j0_;                        \
+    const T* ey_c1_ = (S) + ram_col(ey_j1_, P) - ey_j1_;                        \
+    for (int i = 0; i < P; ++i) {                                               \
+      const T xi = (x)[i];                                                      \
+      _Pragma("unroll")                                                         \
+      for (int r = 0; r < 2; ++r) {                                             \
+        if (r >= (R)) break;                                                    \
+        const int j = r ? ey_j1_ : ey_j0_;                                      \
+        const bool on = i >= j;                                                 \
+        const T s = (r ? ey_c1_ : ey_c0_)[on ? i : j];                          \
+        (acc)[r] += ((b) * (on ? s : T(0))) * xi;                               \
+      }                                                                         \
+    }                                                                           \
   } while (0)
 
 template <typename T, class TINY>
@@ -1734,6 +1762,188 @@ int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, con
   if (int rc = tril_limits(pl, "MALA with a factor", "the factor", "the factor", ey_generic_mala_tril_lds(pl))) return rc;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step,
                           step_vec, d);
+}
+
+// ----------------------------------------------------------------------------------------------- HMC with a fixed metric
+// Euclidean-metric HMC with a fixed inverse metric Sigma = L L^T (Stan's diag_e / dense_e): p ~ N(0, Sigma^-1),
+// K(p) = p^T Sigma p / 2, written in the whitened velocity v = L^T p so that nothing is solved for:
+//   v ~ N(0, I);  h_cur = -t + |v|^2 / 2;  v += eps/2 L^T g;  L times { theta += eps L v;  (t, g) at theta;  v += w L^T g };
+//   h_prop = -t + |v|^2 / 2;  the accept step of k_hmc.
+// The loop body of k_hmc otherwise -- the same Philox streams and fill_normals, so L = I makes k_hmc's draw, and each
+// multiply-add of it: the products run with the step folded into the factor, (eps L_ij) x_j, on a running sum started at
+// the vector they update.  One wave per chain, no row-wave form, n_iters draws per launch on the records of the one-wave
+// kernels.  FORM EY_METRIC_TRIL: k_mala_tril's layout -- the chain's factor staged ONCE per launch behind the three-vector
+// image in ram_col order, chosen as there (G, metric_index, clamped), P <= 128, rows lane and lane + 64; L v is k_ram's
+// column sweep (a lane owns rows), L^T g the transposed sweep (a lane owns columns).  FORM EY_METRIC_DIAG: L = diag(s), s
+// [P] of metric [G, P] staged as the image's fourth vector; any P the image holds.
+__host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, size_t esz) {
+  return form == EY_METRIC_TRIL ? lds_bytes(m, 3, esz) + mh_tril_extra_bytes(m.P, esz) : lds_bytes(m, 4, esz);
+}
+
+// The two halves of a leapfrog step under the metric, written once for both forms.  Each ends with the barrier that lets
+// every lane read what the others wrote (a sweep reads the whole of the other vector).
+// v += w L^T g.  Reads: T, FORM, P, R, lane, S, sd, v, l.
+#define EY_METRIC_KICK(w)                                                                   \
+  do {                                                                                      \
+    const T ey_w_ = (w);                                                                    \
+    if constexpr (FORM == EY_METRIC_TRIL) {                                                 \
+      T acc[2];                                                                             \
+      _Pragma("unroll")                                                                     \
+      for (int r = 0; r < 2; ++r) acc[r] = v[lane + r * WAVE < P ? lane + r * WAVE : P - 1]; \
+      EY_TRIL_TSWEEP(S, l.gr, R, ey_w_, acc);                                               \
+      _Pragma("unroll")                                                                     \
+      for (int r = 0; r < 2; ++r) {                                                         \
+        if (r >= R) break;                                                                  \
+        v[lane + r * WAVE < P ? lane + r * WAVE : P - 1] = acc[r];                          \
+      }                                                                                     \
+    } else {                                                                                \
+      for (int i = lane; i < P; i += WAVE) v[i] = v[i] + (ey_w_ * sd[i]) * l.gr[i];         \
+    }                                                                                       \
+    __syncthreads();                                                                        \
+  } while (0)
+// theta += eps L v.  Reads: T, FORM, P, R, lane, S, sd, v, l, eps.
+#define EY_METRIC_DRIFT()                                                                   \
+  do {                                                                                      \
+    if constexpr (FORM == EY_METRIC_TRIL) {                                                 \
+      T acc[2];                                                                             \
+      _Pragma("unroll")                                                                     \
+      for (int r = 0; r < 2; ++r) acc[r] = l.th[lane + r * WAVE < P ? lane + r * WAVE : P - 1]; \
+      EY_TRIL_SWEEP(S, v, R, eps, acc);                                                     \
+      _Pragma("unroll")                                                                     \
+      for (int r = 0; r < 2; ++r) {                                                         \
+        const int i = lane + r * WAVE;                                                      \
+        if (i < P) l.th[i] = acc[r];                                                        \
+      }                                                                                     \
+    } else {                                                                                \
+      for (int i = lane; i < P; i += WAVE) l.th[i] = l.th[i] + (eps * sd[i]) * v[i];        \
+    }                                                                                       \
+    __syncthreads();                                                                        \
+  } while (0)
+// EY_LEAPFROG under the metric: half a kick, L drifts with an evaluation each (its value left in t), the last kick halved.
+// Reads: what the two halves read, and TINY, m, ht, tc, L.
+#define EY_LEAPFROG_METRIC(t)                                                           \
+  do {                                                                                  \
+    EY_METRIC_KICK(T(0.5) * eps);                                                       \
+    for (int k = 1; k <= L; ++k) {                                                      \
+      EY_METRIC_DRIFT();                                                                \
+      t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);       \
+      const T w = (k < L) ? eps : T(0.5) * eps;                                         \
+      EY_METRIC_KICK(w);                                                                \
+    }                                                                                   \
+  } while (0)
+
+template <typename T, class TINY, int FORM>
+__global__ void __launch_bounds__(WAVE) k_hmc_metric(EyModel m, T* theta, T* target, T* grad, const T* metric, int64_t G,
+                                                     const int* metric_index, const T* v0, const T* u_in, T step,
+                                                     const T* step_vec, int L, int recompute, T* hcur_o, T* hprop_o,
+                                                     const T* temp, uint64_t seed, uint64_t iter0, uint64_t chain_offset,
+                                                     unsigned char* accepted, T* rate_o, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, FORM == EY_METRIC_TRIL ? 3 : 4);
+  const int P = m.P;
+  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 3, sizeof(T)));  // EY_METRIC_TRIL: the packed factor
+  T* sd = l.b;                                                     // EY_METRIC_DIAG: the scales
+  T* v = l.a;
+  const int R = P > WAVE ? 2 : 1;  // the rows (and columns) of a lane: wave-uniform
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  const T eps = step_vec ? step_vec[c] : step;
+  EY_CHAIN_INDEX(g, metric_index);
+  if constexpr (FORM == EY_METRIC_TRIL) {
+    const T* Lg = metric + g * (int64_t)P * P;
+    EY_TRIL_PACK(S, Lg);
+  } else {
+    const T* sg = metric + g * (int64_t)P;
+    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];
+  }
+  (void)S; (void)sd; (void)R;
+  __syncthreads();
+  T t_state = target[c];
+  for (int it = 0; it < run.n_iters; ++it) {  // ey_hmc_metric_run: see k_mala
+    const uint64_t iter = iter0 + (uint64_t)it;
+    // v ~ N(0, I): k_hmc's momentum draw
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    T kin = T(0);
+    if (!v0) fill_normals<T>(v, rn, P);
+    EY_LANE_PASS(P, i, on) {
+      l.th[i] = theta[c * P + i];
+      l.gr[i] = grad[c * P + i];
+      const T vi = v0 ? v0[c * P + i] : v[i];
+      v[i] = vi;
+      const T vz = on ? vi : T(0);
+      kin += vz * vz;
+    }
+    kin = wave_sum(kin);
+    const T h_cur = -t_state + T(0.5) * kin;
+    __syncthreads();
+    T t = t_state;
+    if (recompute) t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
+    EY_LEAPFROG_METRIC(t);
+    kin = T(0);
+    EY_LANE_PASS(P, i, on) {
+      const T vz = on ? v[i] : T(0);
+      kin += vz * vz;
+    }
+    kin = wave_sum(kin);
+    const T h_prop = -t + T(0.5) * kin;
+    T rate = Num<T>::exp(h_cur - h_prop);
+    if (rate > T(1)) rate = T(1);
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    const T u = u_in ? u_in[c] : ey_rng_uniform<T>(ru);
+    const bool acc_ = u < rate;  // strict <; a NaN rate rejects (k_hmc)
+    if (acc_) {
+      t_state = t;
+      for (int i = lane; i < P; i += WAVE) {
+        theta[c * P + i] = l.th[i];
+        grad[c * P + i] = l.gr[i];
+      }
+    }
+    EY_RECORD_SAMPLE(true, i, acc_ ? l.th[i] : theta[c * P + i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, t, t_state, rate, target, accepted, rate_o, run);
+    if (lane == 0) {
+      if (hcur_o) hcur_o[c] = h_cur;
+      if (hprop_o) hprop_o[c] = h_prop;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, class TINY>
+static int launch_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                             const void* metric_index, const void* v0, const void* u, double step, const void* step_vec,
+                             int L, const EyDraw& d, void* hcur, void* hprop) {
+  const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
+  const int recompute = (d.flags & EY_RECOMPUTE_INITIAL_GRAD) != 0;
+  if (form == EY_METRIC_TRIL)
+    return launch(k_hmc_metric<T, TINY, EY_METRIC_TRIL>, d.C, 1, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                  (const T*)metric, G, (const int*)metric_index, (const T*)v0, (const T*)u, (T)step, (const T*)step_vec, L,
+                  recompute, (T*)hcur, (T*)hprop, EY_DRAW_ARGS(T, d));
+  return launch(k_hmc_metric<T, TINY, EY_METRIC_DIAG>, d.C, 1, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                (const T*)metric, G, (const int*)metric_index, (const T*)v0, (const T*)u, (T)step, (const T*)step_vec, L,
+                recompute, (T*)hcur, (T*)hprop, EY_DRAW_ARGS(T, d));
+}
+
+size_t ey_generic_hmc_metric_lds(const ey_plan* pl, int form) {
+  return hmc_metric_lds(pl->m, form, pl->dtype == EY_F32 ? 4 : 8);
+}
+
+// `rate` takes the place of a draw's log_rate: record_draw writes it with the accept flag
+int ey_generic_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                          const void* metric_index, const void* v0, const void* u, double step, const void* step_vec, int L,
+                          const EyDraw& d, void* rate, void* hcur, void* hprop) {
+  const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
+  if (form == EY_METRIC_TRIL) {
+    if (int rc = tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)) return rc;
+  } else if (bytes > 160 * 1024) {
+    EY_FAIL(EY_ERR_UNSUPPORTED, "HMC with a diagonal metric: the model's evaluation image and the scales (" +
+                                    std::to_string(bytes) + " bytes) do not fit the 160 KiB LDS of a CU");
+  }
+  EyDraw dr = d;
+  dr.log_rate = rate;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc_metric, pl, theta, target, grad, metric, form, G, metric_index, v0, u,
+                          step, step_vec, L, dr, hcur, hprop);
 }
 
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs

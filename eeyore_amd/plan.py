@@ -571,6 +571,68 @@ class Plan:
         return self._sample(L.lib().ey_mala_tril_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
                             records=(samples, targets, accepted_rec, accept_count))
 
+    def _metric(self, metric, form, index, C):
+        """(form code, G, index) of an HMC metric for C chains, checked: ``form`` 'diag' with scales [P] or [G, P], 'dense'
+        with lower-triangular factors [P, P] or [G, P, P]; ``index`` as in ``_tril``."""
+        P = self.P
+        if form not in ("diag", "dense"):
+            raise ValueError("form must be 'diag' or 'dense'")
+        if form == "dense":
+            G, index = self._tril(metric, index, C)
+            return L.EY_METRIC_TRIL, G, index
+        if (not torch.is_tensor(metric) or metric.device != self.device or metric.dtype != self.dtype
+                or not metric.is_contiguous() or metric.dim() not in (1, 2) or metric.shape[-1] != P
+                or metric.shape[0] < 1):
+            raise ValueError(f"a diagonal metric must be a contiguous [{P}] or [G, {P}] tensor of the plan's dtype on its "
+                             "device")
+        G = 1 if metric.dim() == 1 else int(metric.shape[0])
+        if index is None:
+            if G not in (1, C):
+                raise ValueError(f"metric holds {G} scale vectors for {C} chains: without index it must hold 1 or {C}")
+            return L.EY_METRIC_DIAG, G, None
+        return L.EY_METRIC_DIAG, G, self._metric_index(index, G, C)
+
+    def _metric_index(self, index, G, C):
+        if (not torch.is_tensor(index) or index.device != self.device or index.dtype != torch.int32
+                or tuple(index.shape) != (C,) or not index.is_contiguous()):
+            raise ValueError(f"index must be a contiguous int32 tensor of shape ({C},) on the plan's device")
+        key = (index.data_ptr(), index._version, G, C)  # as _tril: the range check reads the device once per index
+        if C and getattr(self, "_tril_index_checked", None) != key:
+            if int(index.min()) < 0 or int(index.max()) >= G:
+                raise ValueError(f"index must lie in [0, {G})")
+            self._tril_index_checked = key
+        return index
+
+    def hmc_metric_step(self, theta, target, grad, step, num_steps, metric, form, index=None, v0=None, u=None,
+                        step_vec=None, temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
+        """One HMC draw of every chain under a fixed metric with inverse L L^T (ey_hmc_metric_step,
+        include/eeyore_amd_ext.h): ``form`` 'dense' with ``metric`` a lower-triangular factor L [P, P], one per chain
+        [C, P, P], or [G, P, P] with ``index`` [C] int32 naming each chain's (at most 128 parameters; only the lower
+        triangle is read); ``form`` 'diag' with scales s [P], [C, P] or [G, P], L = diag(s).  ``v0`` [C, P] replaces the
+        draw of the whitened velocity v = L^T p, the rest is ``hmc_step``'s.  Returns accepted, rate, h_cur, h_prop."""
+        C = self._theta(theta)
+        code, G, index = self._metric(metric, form, index, C)
+        if out is None:
+            out = dict(accepted=self.empty(C, dtype=torch.uint8), rate=self.empty(C), h_cur=self.empty(C),
+                       h_prop=self.empty(C))
+        u, step_vec = self._opt(u, C), self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), L.ptr(v0), L.ptr(u),
+                float(step), L.ptr(step_vec), int(num_steps))
+        return self._sample(L.lib().ey_hmc_metric_step, C, lead, temp, seed, it, chain_offset, flags, out,
+                            tail=(L.ptr(out["rate"]), L.ptr(out["h_cur"]), L.ptr(out["h_prop"])))
+
+    def hmc_metric_run(self, theta, target, grad, step, num_steps, metric, form, n_iters, index=None, step_vec=None,
+                       temp=None, seed=0, it=0, chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None,
+                       accept_count=None, out=None):
+        """``n_iters`` iterations of ``hmc_metric_step`` in one launch (ey_hmc_metric_run); records as in ``hmc_run``."""
+        C = self._theta(theta)
+        code, G, index = self._metric(metric, form, index, C)
+        step_vec = self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), float(step),
+                L.ptr(step_vec), int(num_steps))
+        return self._sample(L.lib().ey_hmc_metric_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count))
+
     def _chol(self, chol, C):
         P = self.P
         self._want("chol", chol, (C, P, P), self.dtype,

@@ -146,8 +146,9 @@ class SingleChainSerialSampler(SerialSampler):
         plan.detach_da()
         # a per-chain dual-averaging tuner can run inside the fused kernels' epilogue (ey_plan_attach_da): burn-in is
         # then blocks of iterations per launch too
+        # (not with an HMC metric: ey_hmc_metric_step does not consume the table, the tuner adapts draw by draw)
         in_kernel_da = (hasattr(tuner, 'attach') and plan.kernel in ('mfma32', 'fused16')
-                        and counter.num_burnin_iters > counter.idx)
+                        and counter.num_burnin_iters > counter.idx and getattr(self, '_metric', None) is None)
         if in_kernel_da:
             tuner.attach(plan, counter.num_burnin_iters - counter.idx, idx0=counter.idx)
             self.step = tuner.step

@@ -1,6 +1,7 @@
 import torch
 
-from .base import SingleChainSerialSampler, default_counter
+from .base import TRIL_MAX_P, SingleChainSerialSampler, default_counter
+from .metric import DenseMetric, DiagMetric
 from eeyore_amd.tuners import HMCDATuner, PerChainDATuner
 from eeyore_amd import _lib as L
 
@@ -17,17 +18,30 @@ class HMC(SingleChainSerialSampler):
     ``chain`` defaults to a fresh chain per sampler (the reference's default argument is one ChainList shared by
     every sampler, hmc.py:11).  ``init_step_mode``: how a tuner without a starting step gets one -- 'intended'
     (default: the step-doubling heuristic hmc.py:38-77 set out to write) or 'reference' (what those lines compute,
-    integer powers included; see ``init_step``)."""
+    integer powers included; see ``init_step``).
+
+    ``metric``: a fixed Euclidean metric, ``DiagMetric(scale)`` or ``DenseMetric(scale_tril)`` (Stan's diag_e / dense_e),
+    stating the inverse mass matrix Sigma = L L^T: the momentum is p ~ N(0, Sigma^-1), the kinetic energy p^T Sigma p / 2, and
+    one ``draw`` is one call of ``ey_hmc_metric_step`` (a dense metric: at most 128 parameters).  The kernel works in the
+    whitened velocity v = L^T p, and that is what ``current['momentum']`` holds with a metric (rng='torch'): the momentum
+    itself is p = L^-T v.  A metric per chain is [C, P] / [C, P, P]; ``_set_metric(metric, index)`` takes a table with an
+    int32 [C] index naming each chain's entry, in the manner of ``_set_tril``.  Tuners adapt draw by draw (the in-kernel
+    dual averaging of the fused kernels is not used with a metric), ``init_step_mode='reference'`` and ``leapfrog`` have no
+    metric form and raise ``ValueError``.  Without a metric nothing changes."""
 
     keys = ['sample', 'target_val', 'grad_val', 'momentum', 'hamiltonian', 'accepted']
 
     def __init__(self, model, theta0=None, dataloader=None, data0=None, counter=None, step=0.1, num_steps=10,
                  tuner=None, chain=None, rng=None, seed=0, chain_offset=0, recompute_initial_grad=False,
-                 temperature=None, init_step_mode='intended'):
+                 temperature=None, init_step_mode='intended', metric=None):
         super().__init__(default_counter(counter, dataloader))
         self._configure(model, dataloader, theta0, chain, rng, seed, chain_offset, temperature)
         if init_step_mode not in ('intended', 'reference'):
             raise ValueError("init_step_mode must be 'intended' or 'reference'")
+        if metric is not None and init_step_mode == 'reference':
+            raise ValueError("HMC: init_step_mode='reference' restates the reference's identity-mass heuristic and has no "
+                             "metric form; use 'intended' with a metric")
+        self._set_metric(metric)
         self.tuner = tuner
         self.recompute_initial_grad = recompute_initial_grad
         self.step, self.num_steps = step, num_steps
@@ -75,9 +89,43 @@ class HMC(SingleChainSerialSampler):
         self._publish(torch.zeros(self.num_chains, dtype=torch.uint8))
         self.current['accepted'] = None
 
+    def _set_metric(self, metric, index=None):
+        """Take a ``DiagMetric`` / ``DenseMetric`` (or None: identity mass, the plain kernels) to the device, checked:
+        one entry for all chains, one per chain, or a table of G entries with ``index`` (int32 [C]) naming the entry of
+        every chain."""
+        self.metric = metric
+        self._metric = self._metric_form = self._metric_index = None
+        if metric is None:
+            return
+        if not isinstance(metric, (DiagMetric, DenseMetric)):
+            raise ValueError("HMC: metric must be a DiagMetric or a DenseMetric")
+        P = self.model.num_params()
+        if metric.num_params != P:
+            raise ValueError(f"HMC: the metric is for {metric.num_params} parameters, the model has {P}")
+        if metric.form == 'dense' and P > TRIL_MAX_P:
+            raise ValueError(f"HMC: a DenseMetric is limited to {TRIL_MAX_P} parameters (the model has {P}): the factor "
+                             "lives in LDS; a DiagMetric has no such limit")
+        if index is None and metric.per_chain and metric.table.shape[0] != self.num_chains:
+            raise ValueError(f"HMC: the metric holds {metric.table.shape[0]} entries for {self.num_chains} chains: give "
+                             "one entry or one per chain")
+        self._metric = metric.table.to(device=self.model.device, dtype=self.model.dtype).contiguous()
+        self._metric_form = metric.form
+        if index is not None:
+            self._metric_index = torch.as_tensor(index).to(device=self.model.device, dtype=torch.int32).contiguous()
+
+    def _metric_of(self, c):
+        """Chain c's own entry of the metric table, as a table of one."""
+        if self._metric.dim() == (1 if self._metric_form == 'diag' else 2):
+            return self._metric
+        g = c if self._metric_index is None else int(self._metric_index[c])
+        return self._metric[g].contiguous()
+
     def leapfrog(self, position0, momentum0, x, y):
         """(position_L, momentum_L, target_val, grad_val) as hmc.py:100-124: L steps, L+1 gradient evaluations, the
         final momentum negated."""
+        if self._metric is not None:
+            raise ValueError("HMC.leapfrog has no metric form yet (ey_hmc_leapfrog integrates with identity mass); "
+                             "construct the sampler without a metric to use it")
         single = position0.dim() == 1
         th, p = self._state_tensor(position0), self._state_tensor(momentum0)
         step, step_vec = self._step_args()
@@ -100,11 +148,28 @@ class HMC(SingleChainSerialSampler):
         self.step, self.num_steps = 1., 1
         th = (theta if theta.dim() == 1 else theta[0]).to(self.model.device, self.model.dtype)
         momentum = torch.randn(self.model.num_params(), dtype=self.model.dtype, device=self.model.device)
-        h_start = self.hamiltonian(-self.model.log_target(th.clone(), x, y), momentum)
+        if self._metric is not None:
+            # with a metric: the ratio exp(H_cur - H_prop) of one leapfrog step of ey_hmc_metric_step on cloned state,
+            # `momentum` being the whitened velocity of every trial
+            if not intended:
+                raise ValueError("HMC.init_step: intended=False has no metric form")
+            plan = self.model._plan(x, y)
+            th1 = self._state_tensor(th)
+            temp = self._temp()
+            temp = temp[:1] if torch.is_tensor(temp) and temp.dim() == 1 else temp
+            t1, g1 = plan.log_target_grad(th1, temp=temp)
+            m0, half = self._metric_of(0), torch.full((1,), 0.5, dtype=self.model.dtype, device=self.model.device)
 
-        def ratio_after_one_step():
-            _, p_new, t_new, _ = self.leapfrog(th, momentum, x, y)
-            return torch.exp(h_start - self.hamiltonian(-t_new, p_new)).item()
+            def ratio_after_one_step():
+                out = plan.hmc_metric_step(th1.clone(), t1.clone(), g1.clone(), self.step, 1, m0, self._metric_form,
+                                           v0=momentum[None].contiguous(), u=half, temp=temp)
+                return torch.exp(out['h_cur'] - out['h_prop']).item()
+        else:
+            h_start = self.hamiltonian(-self.model.log_target(th.clone(), x, y), momentum)
+
+            def ratio_after_one_step():
+                _, p_new, t_new, _ = self.leapfrog(th, momentum, x, y)
+                return torch.exp(h_start - self.hamiltonian(-t_new, p_new)).item()
 
         ratio = ratio_after_one_step()
         direction = 1 if ratio > 0.5 else -1
@@ -128,11 +193,16 @@ class HMC(SingleChainSerialSampler):
         th0 = self._state_tensor(theta)
         C, P = th0.shape
         momentum = torch.randn(C, P, dtype=self.model.dtype, device=self.model.device)
-        t0, _ = plan.log_target_grad(th0, temp=self._temp())
+        t0, g0 = plan.log_target_grad(th0, temp=self._temp())
         h_start = -t0 + 0.5 * momentum.pow(2).sum(-1)
         step = torch.ones(C, dtype=self.model.dtype, device=self.model.device)
 
         def ratio_after_one_step():
+            if self._metric is not None:  # one leapfrog step of ey_hmc_metric_step on cloned state, v0 = momentum
+                out = plan.hmc_metric_step(th0.clone(), t0.clone(), g0.clone(), 0.0, 1, self._metric, self._metric_form,
+                                           index=self._metric_index, v0=momentum, u=torch.full_like(step, 0.5),
+                                           step_vec=step, temp=self._temp())
+                return torch.exp(out['h_cur'] - out['h_prop'])
             th, p = th0.clone(), momentum.clone()
             t, _ = plan.leapfrog(th, p, 0.0, 1, step_vec=step, temp=self._temp())
             return torch.exp(h_start - (-t + 0.5 * p.pow(2).sum(-1)))
@@ -149,9 +219,15 @@ class HMC(SingleChainSerialSampler):
 
     def _run_block(self, plan, k, rec):
         step, step_vec = self._step_args()
-        out = plan.hmc_run(self._theta, self._target, self._grad, step, self.num_steps, k, step_vec=step_vec,
-                           temp=self._temp(), seed=self.seed, it=self._iter, chain_offset=self.chain_offset,
-                           flags=L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0, **rec)
+        flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
+        if self._metric is not None:
+            out = plan.hmc_metric_run(self._theta, self._target, self._grad, step, self.num_steps, self._metric,
+                                      self._metric_form, k, index=self._metric_index, step_vec=step_vec, temp=self._temp(),
+                                      seed=self.seed, it=self._iter, chain_offset=self.chain_offset, flags=flags, **rec)
+        else:
+            out = plan.hmc_run(self._theta, self._target, self._grad, step, self.num_steps, k, step_vec=step_vec,
+                               temp=self._temp(), seed=self.seed, it=self._iter, chain_offset=self.chain_offset,
+                               flags=flags, **rec)
         self.current['momentum'] = None
         self.current['hamiltonian'] = None
         return out
@@ -165,9 +241,16 @@ class HMC(SingleChainSerialSampler):
             self._target, self._grad = plan.log_target_grad(self._theta, temp=temp)
         p0, u = self._draw_randoms(*self._theta.shape)
         step, step_vec = self._step_args()
-        out = plan.hmc_step(self._theta, self._target, self._grad, step, self.num_steps, p0=p0, u=u, temp=temp,
-                            step_vec=step_vec, seed=self.seed, it=self._iter, chain_offset=self.chain_offset,
-                            flags=L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0)
+        flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
+        if self._metric is not None:  # p0 is then the whitened velocity v = L^T p
+            out = plan.hmc_metric_step(self._theta, self._target, self._grad, step, self.num_steps, self._metric,
+                                       self._metric_form, index=self._metric_index, v0=p0, u=u, temp=temp,
+                                       step_vec=step_vec, seed=self.seed, it=self._iter, chain_offset=self.chain_offset,
+                                       flags=flags)
+        else:
+            out = plan.hmc_step(self._theta, self._target, self._grad, step, self.num_steps, p0=p0, u=u, temp=temp,
+                                step_vec=step_vec, seed=self.seed, it=self._iter, chain_offset=self.chain_offset,
+                                flags=flags)
         self._publish(out['accepted'])
         self.current['momentum'] = None if p0 is None else self._expose(p0)
         self.current['hamiltonian'] = self._expose(out['h_cur'])

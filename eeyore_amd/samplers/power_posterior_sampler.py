@@ -6,6 +6,7 @@ import torch
 from pathlib import Path
 
 from .hmc import HMC
+from .metric import DenseMetric, DiagMetric
 from .mala import MALA
 from .metropolis_hastings import MetropolisHastings
 from .base import SerialSampler
@@ -40,7 +41,10 @@ class PowerPosteriorSampler(SerialSampler):
     With 'MetropolisHastings' or 'MALA' the kwargs of the temperatures may each hold a ``MultivariateNormalKernel`` with a
     ``[P, P]`` ``scale_tril``: every temperature then proposes with its own factor (the identity where none is given), which stays with
     the temperature when a between-chain move exchanges states.  ``NormalKernel``s are still taken from temperature 0
-    ('MetropolisHastings'; 'MALA' has its default proposal or the factors, nothing else).  All
+    ('MetropolisHastings'; 'MALA' has its default proposal or the factors, nothing else).  With 'HMC' the kwargs may each
+    hold a ``metric`` (all ``DiagMetric``s or all ``DenseMetric``s, each one entry for its temperature's chains): every
+    temperature then integrates under its own metric (the identity where none is given), which likewise stays with the
+    temperature.  All
     temperatures are advanced by ONE fused step: the K x R chains (K temperatures, R independent replicas of the whole
     ladder; ``theta0`` of shape [P] gives R = 1, [R, P] gives R ladders) form one chain batch whose per-chain
     temperature vector goes to the HIP kernel (temperature multiplies log-likelihood and log-prior,
@@ -117,6 +121,27 @@ class PowerPosteriorSampler(SerialSampler):
             return torch.stack([k.scale_tril.detach().to(device=self.device, dtype=self.dtype) if m else eye
                                 for k, m in zip(kernels, mvn)])
 
+        def temperature_metrics():
+            """One HMC metric per temperature from the temperatures' ``metric`` kwargs, as one DiagMetric [K, P] or
+            DenseMetric [K, P, P] table (state row k * R + r uses entry k), or None if no temperature holds one.  All of
+            one kind, each for all of its temperature's chains; a temperature without one gets the identity."""
+            metrics = [k.get('metric') for k in kw]
+            given = [m for m in metrics if m is not None]
+            if not given:
+                return None
+            kind = type(given[0])
+            if kind not in (DiagMetric, DenseMetric) or any(type(m) is not kind for m in given):
+                raise ValueError("the temperatures' metrics must be all DiagMetrics or all DenseMetrics (a temperature "
+                                 "without a metric keeps the identity)")
+            if any(m.per_chain for m in given):
+                raise ValueError("a temperature's metric must hold one entry for all of its chains")
+            P = model.num_params()
+            if any(m.num_params != P for m in given):
+                raise ValueError(f"a temperature's metric must be for the model's {P} parameters")
+            eye = kind.identity(P, dtype=self.dtype, device=self.device).table
+            return kind(torch.stack([eye if m is None else m.table.to(device=self.device, dtype=self.dtype)
+                                     for m in metrics]))
+
         if name == 'MALA':
             self.sampler = MALA(model, step=per_chain('step', 0.1), **common)
             trils = temperature_trils()
@@ -127,6 +152,9 @@ class PowerPosteriorSampler(SerialSampler):
             if len(ns) != 1:
                 raise ValueError("num_steps must be the same at every temperature")
             self.sampler = HMC(model, step=per_chain('step', 0.1), num_steps=ns.pop(), **common)
+            table = temperature_metrics()
+            if table is not None:
+                self.sampler._set_metric(table, index=torch.arange(K, dtype=torch.int32).repeat_interleave(R))
         elif name == 'MetropolisHastings':
             trils = temperature_trils()
             if trils is not None:
