@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h).
+"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -106,6 +106,15 @@ EXT_SYMBOLS = {
     "ey_hmc_metric_run": (_i, [_vp] * 5 + [_i, _i64, _vp, _d, _vp, _i] + _RUN),
 }
 
+# ... and what include/eeyore_amd_warmup.h declares, the warm-up of HMC under a metric: a third table, bound by lib() beside
+# the other two.  ey_hmc_metric_warmup: ey_hmc_metric_run's arguments, then da_state, da_table, da_n, d, log_eub, final_avg,
+# mean, M2, count, steps_rec, rate_rec before the stream.
+WARMUP_SYMBOLS = {
+    "ey_hmc_metric_warmup": (_i, [_vp] * 5 + [_i, _i64, _vp, _d, _vp, _i] + _RUN[:-1]
+                             + [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ey_metric_from_moments": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -136,7 +145,7 @@ def lib():
                 f"eeyore_amd: HIP library {LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C eeyore_amd/csrc`); there is no CPU fallback")
         L = ct.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

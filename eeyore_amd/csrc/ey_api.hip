@@ -1124,6 +1124,52 @@ int ey_hmc_metric_run(ey_plan* pl, void* theta, void* target, void* grad, const 
                          nullptr, nullptr, nullptr, "ey_hmc_metric_run");
 }
 
+// (declared in include/eeyore_amd_warmup.h)  ey_hmc_metric_run's frame and refusals, then those of the two epilogues: all of
+// them before ready(), so a refused call has touched nothing.
+int ey_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                         const void* metric_index, double step, void* step_vec, int L, const void* temp, int64_t C,
+                         uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                         void* targets, void* accepted_rec, void* accept_count, void* accepted, void* da_state,
+                         const void* da_table, int da_n, double d, double log_eub, int final_avg, void* mean, void* M2,
+                         int64_t count, void* steps_rec, void* rate_rec, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw dr = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  EyCall f{pl, dr, "ey_hmc_metric_warmup"};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !grad || !metric || !accepted) return f.refuse("null argument");
+  if (form != EY_METRIC_DIAG && form != EY_METRIC_TRIL)
+    return f.refuse("form must be EY_METRIC_DIAG or EY_METRIC_TRIL");
+  if (L < 1) return f.refuse("num_steps must be >= 1");
+  EY_TRY(f.step(step, step_vec));
+  EY_TRY(f.n_iters());
+  EY_TRY(f.factors(G, metric_index));
+  if (pl->da_state)
+    return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which HMC with a metric does not consume; "
+                    "detach it and pass the dual averaging as arguments of this call");
+  if (da_state && !da_table) return f.refuse("a dual-averaging state (da_state) needs its table (da_table)");
+  if (da_state && !step_vec) return f.refuse("a dual-averaging state (da_state) needs step_vec, the steps it adapts");
+  if (da_state && (da_n < 1 || da_n > n_iters)) return f.refuse("da_n must lie in [1, n_iters]");
+  if (da_state && !std::isfinite(d)) return f.refuse("the target acceptance d must be finite");
+  if (!mean != !M2) return f.refuse("mean and M2 go together: exactly one of them is null");
+  if (mean && count < 0) return f.refuse("count must be >= 0");
+  EY_TRY(f.ready(true));
+  EyWarm w;
+  w.da_state = (double*)da_state;
+  w.da_table = (const double*)da_table;
+  w.da_n = da_state ? da_n : 0;
+  w.final_it = da_state && final_avg ? da_n - 1 : -1;
+  w.d = d;
+  w.has_eub = log_eub == log_eub ? 1 : 0;  // NaN: no upper bound (ey_plan_attach_da)
+  w.logeub = w.has_eub ? log_eub : 0.0;
+  w.mean = (double*)mean;
+  w.M2 = (double*)M2;
+  w.count = count;
+  w.steps_rec = steps_rec;
+  w.rate_rec = rate_rec;
+  return f.finish(ey_generic_hmc_metric_warmup(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, L,
+                                               dr, w), theta);
+}
+
 int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,
                const void* cov0, int cov0_per_chain, double l, double b, double c, double eps, int64_t t0, int64_t idx,
                int64_t offset, const void* z, const void* u_mix, const void* u, const void* temp, int64_t C,

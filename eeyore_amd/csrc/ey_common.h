@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <string>
 
-#include "../../include/eeyore_amd_ext.h"  // includes eeyore_amd.h
+#include "../../include/eeyore_amd_warmup.h"  // includes eeyore_amd.h and eeyore_amd_ext.h
 
 #define EY_MAX_LAYERS 8
 #define EY_VERSION 200  // 0.2.0
@@ -225,6 +225,22 @@ size_t ey_generic_hmc_metric_lds(const ey_plan* pl, int form);  // dynamic LDS o
 int ey_generic_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
                           const void* metric_index, const void* v0, const void* u, double step, const void* step_vec, int L,
                           const EyDraw& d, void* rate, void* hcur, void* hprop);
+// the warm-up form of the metric draw loop (k_hmc_metric_warmup): what a launch adds to ey_generic_hmc_metric's run of
+// draws, every pointer optional.  The dual averaging is EyDA's, as arguments of the call.
+struct EyWarm {
+  double* da_state;        // [C,3]: barh, logbare, mu; null: no dual averaging
+  const double* da_table;  // [da_n,3]: first row = this launch's first draw
+  int da_n;                // adapting draws in this launch (the rest of the launch keeps the last step)
+  int final_it;            // launch-local draw that stores exp(logbare) instead of exp(loge); -1 = none
+  double d, logeub;
+  int has_eub;
+  double *mean, *M2;       // [C,P] and [C,P] (EY_METRIC_DIAG) or [C,P,P] (EY_METRIC_TRIL, j <= i only); null: no moments
+  int64_t count;           // draws already in the moments
+  void *steps_rec, *rate_rec;  // [n_iters,C] of the plan's dtype, or null
+};
+int ey_generic_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form,
+                                 int64_t G, const void* metric_index, double step, void* step_vec, int L, const EyDraw& d,
+                                 const EyWarm& w);
 
 #define EY_AM_RIDGE 0
 #define EY_AM_SOFTABS 1

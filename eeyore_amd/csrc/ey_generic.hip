@@ -1946,6 +1946,174 @@ int ey_generic_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, co
                           step, step_vec, L, dr, hcur, hprop);
 }
 
+// ----------------------------------------------------------------------------------- HMC under a metric: the warm-up form
+// k_hmc_metric's draw loop on its own Philox streams (no v0, no u: ey_hmc_metric_run's draws, expression for expression, so
+// that a launch with nothing attached leaves its bits), with two optional epilogues after each draw's accept step
+// (DESIGN.md 4.23).  A sibling kernel, not a parameter of k_hmc_metric: that kernel and its instantiations stay as they are.
+//  Dual averaging: every lane runs ey_da_update on the draw's rate from the chain's state in registers (the same inputs in
+//    every lane, hence the same step in every lane: nothing is broadcast), lane 0 writes the step of the next draw to
+//    step_vec[c]; the state goes back to memory once, after the last draw.
+//  Welford moments of the state the chain is left in, in double, in global memory.  EY_METRIC_DIAG: one pass, a lane owns
+//    elements lane, lane + 64, ... of mean and M2 (EY_LANE_PASS: contiguous across the wave).  EY_METRIC_TRIL: the same pass
+//    leaves dlt = x - mean_old as doubles in LDS, over l.gr and l.a, which hold nothing between the accept step and the next
+//    draw's loads (8 P bytes <= the two vectors in either dtype); then row i of M2 is updated for j <= i with the lanes
+//    along j, 64 columns a round: a round beyond the diagonal is skipped (wave-uniform), a lane beyond it inside a round
+//    takes the diagonal element and repeats its owner's work on the same inputs.  The strict upper triangle is never
+//    touched.  No atomics; every sum's order depends on P alone.
+template <typename T, class TINY, int FORM>
+__global__ void __launch_bounds__(WAVE) k_hmc_metric_warmup(EyModel m, T* theta, T* target, T* grad, const T* metric,
+                                                            int64_t G, const int* metric_index, T step, T* step_vec, int L,
+                                                            int recompute, EyWarm w, const T* temp, uint64_t seed,
+                                                            uint64_t iter0, uint64_t chain_offset, unsigned char* accepted,
+                                                            T* rate_o, EyRun run, int64_t C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const Lds<T> l = carve<T>(m, smem, FORM == EY_METRIC_TRIL ? 3 : 4);
+  const int P = m.P;
+  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 3, sizeof(T)));  // EY_METRIC_TRIL: the packed factor
+  T* sd = l.b;                                                     // EY_METRIC_DIAG: the scales
+  T* v = l.a;
+  double* dlt = reinterpret_cast<double*>(l.gr);                   // EY_METRIC_TRIL moments: x - mean_old, between draws
+  const int R = P > WAVE ? 2 : 1;  // the rows (and columns) of a lane: wave-uniform
+  const int64_t c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool ht = temp != nullptr;
+  const T tc = ht ? temp[c] : T(1);
+  T eps = step_vec ? step_vec[c] : step;
+  EY_CHAIN_INDEX(g, metric_index);
+  if constexpr (FORM == EY_METRIC_TRIL) {
+    const T* Lg = metric + g * (int64_t)P * P;
+    EY_TRIL_PACK(S, Lg);
+  } else {
+    const T* sg = metric + g * (int64_t)P;
+    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];
+  }
+  (void)S; (void)sd; (void)R; (void)dlt;
+  double da[3] = {0.0, 0.0, 0.0};
+  if (w.da_state) {
+    for (int k = 0; k < 3; ++k) da[k] = w.da_state[3 * c + k];
+  }
+  double* mean_c = w.mean ? w.mean + c * (int64_t)P : nullptr;
+  double* M2_c = w.M2 ? w.M2 + c * (FORM == EY_METRIC_TRIL ? (int64_t)P * P : (int64_t)P) : nullptr;
+  __syncthreads();
+  T t_state = target[c];
+  for (int it = 0; it < run.n_iters; ++it) {
+    const uint64_t iter = iter0 + (uint64_t)it;
+    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
+    T kin = T(0);
+    fill_normals<T>(v, rn, P);
+    EY_LANE_PASS(P, i, on) {
+      l.th[i] = theta[c * P + i];
+      l.gr[i] = grad[c * P + i];
+      const T vi = v[i];
+      v[i] = vi;
+      const T vz = on ? vi : T(0);
+      kin += vz * vz;
+    }
+    kin = wave_sum(kin);
+    const T h_cur = -t_state + T(0.5) * kin;
+    __syncthreads();
+    T t = t_state;
+    if (recompute) t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
+    EY_LEAPFROG_METRIC(t);
+    kin = T(0);
+    EY_LANE_PASS(P, i, on) {
+      const T vz = on ? v[i] : T(0);
+      kin += vz * vz;
+    }
+    kin = wave_sum(kin);
+    const T h_prop = -t + T(0.5) * kin;
+    T rate = Num<T>::exp(h_cur - h_prop);
+    if (rate > T(1)) rate = T(1);
+    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
+    const T u = ey_rng_uniform<T>(ru);
+    const bool acc_ = u < rate;  // strict <; a NaN rate rejects (k_hmc)
+    if (acc_) {
+      t_state = t;
+      for (int i = lane; i < P; i += WAVE) {
+        theta[c * P + i] = l.th[i];
+        grad[c * P + i] = l.gr[i];
+      }
+    }
+    EY_RECORD_SAMPLE(true, i, acc_ ? l.th[i] : theta[c * P + i]);
+    record_draw<T>(lane == 0, c, it, C, acc_, t, t_state, rate, target, accepted, rate_o, run);
+    if (lane == 0) {
+      if (w.steps_rec) static_cast<T*>(w.steps_rec)[(int64_t)it * C + c] = eps;
+      if (w.rate_rec) static_cast<T*>(w.rate_rec)[(int64_t)it * C + c] = rate;
+    }
+    if (w.da_state && it < w.da_n) {  // wave-uniform
+      eps = (T)ey_da_update(da, w.da_table + 3 * it, (double)rate, w.d, w.has_eub != 0, w.logeub, it == w.final_it);
+      if (lane == 0) step_vec[c] = eps;
+    }
+    if (mean_c) {  // wave-uniform
+      const double n = (double)(w.count + it + 1);
+      const double f = (n - 1.0) / n;
+      if constexpr (FORM == EY_METRIC_TRIL) __syncthreads();  // l.gr has been read for the last time: dlt takes its place
+      EY_LANE_PASS(P, i, on) {
+        (void)on;
+        const double x = (double)(acc_ ? l.th[i] : theta[c * P + i]);
+        const double mu = mean_c[i];
+        const double dx = x - mu;
+        mean_c[i] = mu + dx / n;
+        if constexpr (FORM == EY_METRIC_TRIL) {
+          dlt[i] = dx;
+        } else {
+          M2_c[i] = M2_c[i] + f * (dx * dx);
+        }
+      }
+      if constexpr (FORM == EY_METRIC_TRIL) {
+        __syncthreads();
+        for (int i = 0; i < P; ++i) {
+          const double fi = f * dlt[i];
+          double* row = M2_c + (int64_t)i * P;
+          _Pragma("unroll")
+          for (int r = 0; r < 2; ++r) {
+            if (r * WAVE > i) break;  // a round wholly beyond the diagonal: wave-uniform
+            const int j = lane + r * WAVE;
+            const int jj = j <= i ? j : i;
+            row[jj] = row[jj] + fi * dlt[jj];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (w.da_state && lane == 0) {
+    w.da_state[3 * c] = da[0];
+    w.da_state[3 * c + 1] = da[1];
+  }
+}
+
+template <typename T, class TINY>
+static int launch_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form,
+                                    int64_t G, const void* metric_index, double step, void* step_vec, int L,
+                                    const EyDraw& d, const EyWarm& w) {
+  const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
+  const int recompute = (d.flags & EY_RECOMPUTE_INITIAL_GRAD) != 0;
+  if (form == EY_METRIC_TRIL)
+    return launch(k_hmc_metric_warmup<T, TINY, EY_METRIC_TRIL>, d.C, 1, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                  (const T*)metric, G, (const int*)metric_index, (T)step, (T*)step_vec, L, recompute, w,
+                  EY_DRAW_ARGS(T, d));
+  return launch(k_hmc_metric_warmup<T, TINY, EY_METRIC_DIAG>, d.C, 1, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
+                (const T*)metric, G, (const int*)metric_index, (T)step, (T*)step_vec, L, recompute, w, EY_DRAW_ARGS(T, d));
+}
+
+// the limits and the LDS image are ey_generic_hmc_metric's: the moments live in global memory
+int ey_generic_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form,
+                                 int64_t G, const void* metric_index, double step, void* step_vec, int L, const EyDraw& d,
+                                 const EyWarm& w) {
+  const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
+  if (form == EY_METRIC_TRIL) {
+    if (int rc = tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)) return rc;
+  } else if (bytes > 160 * 1024) {
+    EY_FAIL(EY_ERR_UNSUPPORTED, "HMC with a diagonal metric: the model's evaluation image and the scales (" +
+                                    std::to_string(bytes) + " bytes) do not fit the 160 KiB LDS of a CU");
+  }
+  EyDraw dr = d;
+  dr.log_rate = nullptr;
+  return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc_metric_warmup, pl, theta, target, grad, metric, form, G, metric_index,
+                          step, step_vec, L, dr, w);
+}
+
 // ----------------------------------------------------------------------------------------------- Metropolis within Gibbs
 // Gibbs.draw (eeyore/samplers/gibbs.py:67-102): per draw, S accept/reject sub-steps, each a Normal random-walk proposal
 // for one block of parameters and one evaluation of the whole log-target.  The kernel knows nothing of nodes: it walks a

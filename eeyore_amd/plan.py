@@ -633,6 +633,74 @@ class Plan:
         return self._sample(L.lib().ey_hmc_metric_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
                             records=(samples, targets, accepted_rec, accept_count))
 
+    def hmc_metric_warmup(self, theta, target, grad, step, num_steps, metric, form, n_iters, index=None, step_vec=None,
+                          temp=None, seed=0, it=0, chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None,
+                          accept_count=None, out=None, da_state=None, da_table=None, d=0.8, log_eub=None, final_avg=False,
+                          mean=None, M2=None, count=0, steps_rec=None, rate_rec=None):
+        """``n_iters`` draws of ``hmc_metric_run`` in one launch that also adapt (ey_hmc_metric_warmup,
+        include/eeyore_amd_warmup.h).  ``da_state`` [C, 3] float64 (barh, logbare, mu) with ``da_table`` [k, 3] float64,
+        k <= n_iters rows (1/(t + t0), sqrt(t)/gamma, t^-kappa) for the launch's first k draws: dual averaging of every
+        chain's step towards the acceptance ``d``, capped at exp(``log_eub``); ``step_vec`` [C] (a tensor of the plan's
+        dtype, required then) is read and written in place, with ``final_avg`` draw k - 1 leaves the averaged step.
+        ``mean`` [C, P] and ``M2`` [C, P] ('diag') or [C, P, P] ('dense', the lower triangle only) float64: Welford moments of
+        the state each chain is left in, ``count`` draws already in them.  ``steps_rec`` / ``rate_rec`` [n_iters, C]: the
+        step each draw used and its acceptance rate.  With none of these it is ``hmc_metric_run``, bit for bit."""
+        C = self._theta(theta)
+        code, G, index = self._metric(metric, form, index, C)
+        n_iters, f64 = int(n_iters), torch.float64
+        if da_state is not None or steps_rec is not None:
+            if step_vec is not None:  # in/out: the caller's own tensor, not a converted copy
+                self._want("step_vec", step_vec, (C,), self.dtype)
+        else:
+            step_vec = self._opt(step_vec, C)
+        if da_state is not None:
+            self._want("da_state", da_state, (C, 3), f64)
+            if da_table is not None:
+                self._want("da_table", da_table, (da_table.shape[0], 3), f64)
+        for name, t, shape in (("mean", mean, (C, self.P)),
+                               ("M2", M2, (C, self.P) if form == "diag" else (C, self.P, self.P))):
+            if t is not None:
+                self._want(name, t, shape, f64)
+        for name, t in (("steps_rec", steps_rec), ("rate_rec", rate_rec)):
+            if t is not None:
+                self._want(name, t, (n_iters, C), self.dtype)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), float(step),
+                L.ptr(step_vec), int(num_steps))
+        tail = (L.ptr(da_state), L.ptr(da_table), 0 if da_table is None else int(da_table.shape[0]), float(d),
+                float('nan') if log_eub is None else float(log_eub), int(bool(final_avg)), L.ptr(mean), L.ptr(M2),
+                int(count), L.ptr(steps_rec), L.ptr(rate_rec))
+        return self._sample(L.lib().ey_hmc_metric_warmup, C, lead, temp, seed, it, chain_offset, flags, out,
+                            n_iters=n_iters, records=(samples, targets, accepted_rec, accept_count), tail=tail)
+
+    def metric_from_moments(self, mean, M2, n, form, pooled=True, table=None, status=None):
+        """A metric table of the plan's dtype from the running moments ``hmc_metric_warmup`` leaves after ``n`` draws of
+        every chain (ey_metric_from_moments): Stan's regularised estimate as ``DiagMetric`` / ``DenseMetric.from_samples``
+        define it, one for all chains (``pooled``: [P] or [P, P], the chains summed in index order) or one per chain
+        ([C, P] or [C, P, P]).  Returns (table, status): status int32 per entry, 0 fine, 1 a non-finite input or a pivot
+        that is not positive -- that entry of ``table`` (the caller's, or a new one of zeros) is then left untouched."""
+        if form not in ("diag", "dense"):
+            raise ValueError("form must be 'diag' or 'dense'")
+        P, f64 = self.P, torch.float64
+        if not torch.is_tensor(mean) or mean.dim() != 2:
+            raise ValueError(f"mean must be a [C, {P}] float64 tensor")
+        C = int(mean.shape[0])
+        self._want("mean", mean, (C, P), f64)
+        self._want("M2", M2, (C, P) if form == "diag" else (C, P, P), f64)
+        entries = 1 if pooled else C
+        shape = ((P,) if form == "diag" else (P, P)) if pooled else ((C, P) if form == "diag" else (C, P, P))
+        if table is None:
+            table = torch.zeros(shape, dtype=self.dtype, device=self.device)
+        self._want("table", table, shape, self.dtype)
+        if status is None:
+            status = torch.zeros(entries, dtype=torch.int32, device=self.device)
+        self._want("status", status, (entries,), torch.int32)
+        with torch.cuda.device(self.device):  # the entry point takes no plan: it runs on the current device
+            L.check(L.lib().ey_metric_from_moments(L.ptr(mean), L.ptr(M2), int(n), C, P,
+                                                   L.EY_METRIC_DIAG if form == "diag" else L.EY_METRIC_TRIL,
+                                                   int(bool(pooled)), _DT[self.dtype], L.ptr(table), L.ptr(status),
+                                                   _stream(self.device)), "ey_metric_from_moments")
+        return table, status
+
     def _chol(self, chol, C):
         P = self.P
         self._want("chol", chol, (C, P, P), self.dtype,

@@ -2,7 +2,7 @@ import torch
 
 from .base import TRIL_MAX_P, SingleChainSerialSampler, default_counter
 from .metric import DenseMetric, DiagMetric
-from eeyore_amd.tuners import HMCDATuner, PerChainDATuner
+from eeyore_amd.tuners import HMCDATuner, PerChainDATuner, WindowedAdaptation
 from eeyore_amd import _lib as L
 
 
@@ -27,7 +27,15 @@ class HMC(SingleChainSerialSampler):
     itself is p = L^-T v.  A metric per chain is [C, P] / [C, P, P]; ``_set_metric(metric, index)`` takes a table with an
     int32 [C] index naming each chain's entry, in the manner of ``_set_tril``.  Tuners adapt draw by draw (the in-kernel
     dual averaging of the fused kernels is not used with a metric), ``init_step_mode='reference'`` and ``leapfrog`` have no
-    metric form and raise ``ValueError``.  Without a metric nothing changes."""
+    metric form and raise ``ValueError``.  Without a metric nothing changes.
+
+    ``tuner=WindowedAdaptation(num_steps, ...)`` with a metric: ``run`` makes the whole burn-in Stan's warm-up on the device
+    (ey_hmc_metric_warmup, ey_metric_from_moments) -- a handful of launches that adapt each chain's step by
+    dual averaging and re-estimate the metric at the end of doubling windows from moments kept inside the kernel, nothing
+    stored or read back between draws.  ``metric`` is the starting metric and its form the form adapted; 'diag' / 'dense'
+    are shorthands for the identity of that form.  After burn-in ``metric`` is the adapted ``DiagMetric`` / ``DenseMetric``,
+    ``step`` the [C] averaged steps, and the run goes on as any run under a fixed metric.  It needs C chains on the in-kernel
+    streams with a full batch: ``ValueError`` otherwise, saying which condition failed."""
 
     keys = ['sample', 'target_val', 'grad_val', 'momentum', 'hamiltonian', 'accepted']
 
@@ -41,6 +49,11 @@ class HMC(SingleChainSerialSampler):
         if metric is not None and init_step_mode == 'reference':
             raise ValueError("HMC: init_step_mode='reference' restates the reference's identity-mass heuristic and has no "
                              "metric form; use 'intended' with a metric")
+        if isinstance(metric, str):  # the identity of that form
+            if metric not in ('diag', 'dense'):
+                raise ValueError("HMC: metric must be a DiagMetric, a DenseMetric, 'diag' or 'dense'")
+            metric = (DiagMetric if metric == 'diag' else DenseMetric).identity(
+                model.num_params(), dtype=model.dtype, device=model.device)
         self._set_metric(metric)
         self.tuner = tuner
         self.recompute_initial_grad = recompute_initial_grad
@@ -62,6 +75,9 @@ class HMC(SingleChainSerialSampler):
             self.num_steps = tuner.num_steps(self.step)
         elif isinstance(tuner, PerChainDATuner):
             self.step, self.num_steps = tuner.step, tuner.num_steps()
+        elif isinstance(tuner, WindowedAdaptation):
+            self.num_steps = tuner.num_steps()
+            self._check_windowed(False)
         if theta0 is not None:
             self.set_current(theta0.clone().detach(), data=data0)
 
@@ -184,15 +200,22 @@ class HMC(SingleChainSerialSampler):
             ratio = ratio_after_one_step()
         self.step = float(self.step)
 
-    def init_step_per_chain(self, theta, max_trials=60):
+    def init_step_per_chain(self, theta, max_trials=60, momentum=None):
         """One starting step size PER CHAIN for ``theta`` [C, P]: Hoffman & Gelman's heuristic
         (2014, algorithm 4) for every chain at once -- each trial is one launch of ``ey_hmc_leapfrog`` with the per-chain
-        step vector; chains whose ratio has crossed 1/2 keep their step.  Returns steps [C] on the device."""
+        step vector; chains whose ratio has crossed 1/2 keep their step.  ``momentum`` [C, P]: the momentum of every trial
+        (with a metric: the whitened velocity); default: drawn from the global torch generator.  Returns steps [C] on the
+        device."""
         x, y = next(iter(self.dataloader))
         plan = self.model._plan(x, y)
         th0 = self._state_tensor(theta)
         C, P = th0.shape
-        momentum = torch.randn(C, P, dtype=self.model.dtype, device=self.model.device)
+        if momentum is None:
+            momentum = torch.randn(C, P, dtype=self.model.dtype, device=self.model.device)
+        elif (tuple(momentum.shape) != (C, P) or momentum.dtype != self.model.dtype or momentum.device != th0.device
+              or not momentum.is_contiguous()):
+            raise ValueError(f"init_step_per_chain: momentum must be a contiguous [{C}, {P}] tensor of the model's dtype on "
+                             "its device")
         t0, g0 = plan.log_target_grad(th0, temp=self._temp())
         h_start = -t0 + 0.5 * momentum.pow(2).sum(-1)
         step = torch.ones(C, dtype=self.model.dtype, device=self.model.device)
@@ -216,6 +239,62 @@ class HMC(SingleChainSerialSampler):
             step = torch.where(active, step * torch.pow(2.0, direction), step)
             ratio = torch.nan_to_num(ratio_after_one_step(), nan=0.0)
         return step
+
+    # -- the windowed warm-up (tuners.WindowedAdaptation)
+    def _check_windowed(self, verbose):
+        """ValueError unless the warm-up can run in blocks: each message names the condition that failed."""
+        who = "HMC with tuner=WindowedAdaptation"
+        if not self.batched:
+            raise ValueError(f"{who}: one chain (theta0 of shape [P]) cannot be warmed up in blocks; give theta0 of shape "
+                             "[C, P]")
+        if self.rng != 'philox':
+            raise ValueError(f"{who}: rng='torch' draws on the host; the warm-up runs on the in-kernel streams "
+                             "(rng='philox')")
+        if self.counter is not None and getattr(self.counter, 'num_batches', 1) != 1:
+            raise ValueError(f"{who}: minibatches ({self.counter.num_batches} batches per epoch) change the target between "
+                             "draws; the warm-up needs the full batch")
+        if verbose:
+            raise ValueError(f"{who}: verbose=True prints between draws; the warm-up runs whole blocks of draws per launch")
+        if self._metric is None:
+            raise ValueError(f"{who}: no metric given; pass metric='diag', 'dense' or a starting DiagMetric / DenseMetric")
+        if self.tuner.pooled:
+            temp = self._temp()
+            if torch.is_tensor(temp) and temp.dim() == 1:
+                raise ValueError(f"{who}: pooled=True estimates one metric from all chains, which a per-chain temperature "
+                                 "vector makes samples of different targets; use pooled=False")
+            if self._metric_index is not None:
+                raise ValueError(f"{who}: pooled=True estimates one metric from all chains, which a metric index table "
+                                 "gives different metrics; use pooled=False")
+
+    def run(self, num_epochs, num_burnin_epochs, verbose=False, verbose_step=100):
+        """As ``SingleChainSerialSampler.run``; with ``tuner=WindowedAdaptation`` the burn-in is the tuner's warm-up, a few
+        launches per window, and the sampling phase the blocks of ``ey_hmc_metric_run`` of any run under a metric."""
+        if not isinstance(self.tuner, WindowedAdaptation):
+            return super().run(num_epochs, num_burnin_epochs, verbose=verbose, verbose_step=verbose_step)
+        self._check_windowed(verbose)
+        counter = self.counter
+        counter.set_epoch_info(num_epochs, num_burnin_epochs)
+        x, y = next(iter(self.dataloader))
+        plan = self.model._plan(x, y)
+        plan.detach_da()
+
+        def advance(k):
+            for _ in range(k):
+                counter.increment_idx()
+
+        if counter.idx < counter.num_burnin_iters:
+            self.tuner.warm_up(self, plan, counter.num_burnin_iters - counter.idx, on_block=advance)
+            self._publish(self.last['accepted'])
+            self.current['momentum'] = self.current['hamiltonian'] = None
+        fuse = self._can_fuse(False)
+        while counter.idx < counter.num_iters:
+            if fuse:
+                k = min(self.fused_block, counter.num_iters - counter.idx)
+                self._draw_block(x, y, k, savestate=True)
+            else:
+                k = 1
+                self.draw(x, y, savestate=True)
+            advance(k)
 
     def _run_block(self, plan, k, rec):
         step, step_vec = self._step_args()

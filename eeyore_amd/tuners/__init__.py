@@ -1,1 +1,2 @@
 from .dual_averaging import HMCDATuner, PerChainDATuner, Tuner
+from .windowed import WindowedAdaptation
