@@ -489,17 +489,14 @@ int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stre
   EyModel& m = pl->m;
   const size_t es = esize(pl);
   const int P = m.P;
-  EY_HIP(hipStreamSynchronize(s));
-  if (!pl->d_mu) EY_HIP(hipMalloc(&pl->d_mu, es * P));
-  if (!pl->d_inv_var) EY_HIP(hipMalloc(&pl->d_inv_var, es * P));
-  std::vector<unsigned char> hs(es * P);
-  EY_HIP(hipMemcpyAsync(pl->d_mu, mu, es * P, hipMemcpyDeviceToDevice, s));
+  std::vector<unsigned char> hs(es * P), hm(es * P);
   EY_HIP(hipMemcpyAsync(hs.data(), sigma, es * P, hipMemcpyDeviceToHost, s));
-  std::vector<unsigned char> hm(es * P);
   EY_HIP(hipMemcpyAsync(hm.data(), mu, es * P, hipMemcpyDeviceToHost, s));
   EY_HIP(hipStreamSynchronize(s));
   // Normal.log_prob = -(v-mu)^2/(2 sigma^2) - log(sigma) - log(sqrt(2 pi)); the theta-independent part is
   // summed once here (in double), the quadratic part is evaluated per call with 1/sigma^2.
+  // Everything is validated before the plan is touched, as in ey_plan_set_prior_family: a refused call leaves the prior
+  // it had (mu included: the kernels that read the prior per element read d_mu).
   double c = 0.0;
   std::vector<unsigned char> hiv(es * P);
   for (int i = 0; i < P; ++i) {
@@ -509,6 +506,9 @@ int ey_plan_set_prior(ey_plan* pl, const void* mu, const void* sigma, void* stre
     if (es == 4) ((float*)hiv.data())[i] = 1.0f / ((float)sg * (float)sg);
     else ((double*)hiv.data())[i] = 1.0 / (sg * sg);
   }
+  if (!pl->d_mu) EY_HIP(hipMalloc(&pl->d_mu, es * P));
+  if (!pl->d_inv_var) EY_HIP(hipMalloc(&pl->d_inv_var, es * P));
+  EY_HIP(hipMemcpy(pl->d_mu, hm.data(), es * P, hipMemcpyHostToDevice));  // the stream is idle: synchronised above
   EY_HIP(hipMemcpy(pl->d_inv_var, hiv.data(), es * P, hipMemcpyHostToDevice));
   // one (mu, sigma) for every parameter (the usual N(0, s) prior): the fused kernel then needs no per-element loads
   pl->prior_uniform = P > 0 && memcmp(hm.data(), hm.data() + es, es * (P - 1)) == 0 &&

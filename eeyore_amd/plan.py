@@ -520,15 +520,24 @@ class Plan:
             if G not in (1, C):
                 raise ValueError(f"tril holds {G} factors for {C} chains: without index it must hold 1 or {C}")
             return G, None
+        return G, self._index(index, G, C)
+
+    def _index(self, index, G, C):
+        """``index`` as ``_tril`` and ``_metric`` take it, checked: an int32 [C] tensor on the device with every entry in
+        [0, G).  The range check reads the device, so it runs once per index, not per draw: it is skipped only when the
+        SAME tensor object, unmodified (``_version``), comes again for the same G and C.  The plan keeps a reference to the
+        tensor it checked, as ``set_data`` does, so that its address cannot be recycled for another index while the key
+        is live."""
         if (not torch.is_tensor(index) or index.device != self.device or index.dtype != torch.int32
                 or tuple(index.shape) != (C,) or not index.is_contiguous()):
             raise ValueError(f"index must be a contiguous int32 tensor of shape ({C},) on the plan's device")
-        key = (index.data_ptr(), index._version, G, C)  # the range check reads the device: once per index, not per draw
-        if C and getattr(self, "_tril_index_checked", None) != key:
+        key = (index._version, G, C)
+        seen = getattr(self, "_tril_index_checked", None)
+        if C and not (seen is not None and seen[0] is index and seen[1] == key):
             if int(index.min()) < 0 or int(index.max()) >= G:
                 raise ValueError(f"index must lie in [0, {G})")
-            self._tril_index_checked = key
-        return G, index
+            self._tril_index_checked = (index, key)
+        return index
 
     def mh_tril_step(self, theta, target, tril, index=None, z=None, u=None, temp=None, seed=0, it=0, chain_offset=0,
                      flags=0, out=None):
@@ -590,18 +599,7 @@ class Plan:
             if G not in (1, C):
                 raise ValueError(f"metric holds {G} scale vectors for {C} chains: without index it must hold 1 or {C}")
             return L.EY_METRIC_DIAG, G, None
-        return L.EY_METRIC_DIAG, G, self._metric_index(index, G, C)
-
-    def _metric_index(self, index, G, C):
-        if (not torch.is_tensor(index) or index.device != self.device or index.dtype != torch.int32
-                or tuple(index.shape) != (C,) or not index.is_contiguous()):
-            raise ValueError(f"index must be a contiguous int32 tensor of shape ({C},) on the plan's device")
-        key = (index.data_ptr(), index._version, G, C)  # as _tril: the range check reads the device once per index
-        if C and getattr(self, "_tril_index_checked", None) != key:
-            if int(index.min()) < 0 or int(index.max()) >= G:
-                raise ValueError(f"index must lie in [0, {G})")
-            self._tril_index_checked = key
-        return index
+        return L.EY_METRIC_DIAG, G, self._index(index, G, C)
 
     def hmc_metric_step(self, theta, target, grad, step, num_steps, metric, form, index=None, v0=None, u=None,
                         step_vec=None, temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
