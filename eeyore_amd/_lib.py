@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h).
+"""ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
+include/eeyore_amd_nuts.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -115,6 +116,18 @@ WARMUP_SYMBOLS = {
     "ey_metric_from_moments": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp]),
 }
 
+# ... and what include/eeyore_amd_nuts.h declares, the No-U-Turn sampler under a metric: a fourth table.  The outputs of a
+# draw (_NUTS_OUT) follow accepted: depth, n_leapfrog, divergent, accept_stat, energy; a run adds depth_rec, divergent_rec;
+# the warm-up then takes ey_hmc_metric_warmup's tail.
+EY_NUTS_MAX_DEPTH = 10
+_NUTS_OUT = [_vp] * 5
+NUTS_SYMBOLS = {
+    "ey_nuts_step": (_i, [_vp] * 5 + [_i, _i64] + [_vp] * 3 + [_i64, _d, _vp, _i] + _DRAW + [_vp] + _NUTS_OUT + [_vp]),
+    "ey_nuts_run": (_i, [_vp] * 5 + [_i, _i64, _vp, _d, _vp, _i] + _RUN[:-1] + _NUTS_OUT + [_vp] * 3),
+    "ey_nuts_warmup": (_i, [_vp] * 5 + [_i, _i64, _vp, _d, _vp, _i] + _RUN[:-1] + _NUTS_OUT + [_vp] * 2
+                       + [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -145,7 +158,8 @@ def lib():
                 f"eeyore_amd: HIP library {LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C eeyore_amd/csrc`); there is no CPU fallback")
         L = ct.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items()):
+        for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
+                                  + list(NUTS_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

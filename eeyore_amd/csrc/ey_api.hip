@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ey_common.h"
+#include "ey_nuts.h"
 
 static thread_local std::string g_err;
 void ey_set_error(const std::string& msg) { g_err = msg; }
@@ -977,6 +978,52 @@ static int hmc_metric_impl(ey_plan* pl, void* theta, void* target, void* grad, c
                                         d, rate, hcur, hprop), theta);
 }
 
+// NUTS under a metric (include/eeyore_amd_nuts.h): hmc_metric_impl's frame and refusals on k_nuts (ey_nuts.hip), then those
+// of the depth cap, the uniform table and the two warm-up epilogues (ey_hmc_metric_warmup's): all of them before ready(), so
+// a refused call has launched and written nothing.
+static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                     const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
+                     void* da_state, const void* da_table, int da_n, double da_d, double log_eub, int final_avg, void* mean,
+                     void* M2, int64_t count, void* steps_rec, void* rate_rec, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin()) return done(rc);
+  if (!theta || !target || !grad || !metric || !d.accepted) return f.refuse("null argument");
+  if (form != EY_METRIC_DIAG && form != EY_METRIC_TRIL)
+    return f.refuse("form must be EY_METRIC_DIAG or EY_METRIC_TRIL");
+  if (nu.max_depth < 1 || nu.max_depth > EY_NUTS_MAX_DEPTH)
+    return f.refuse("max_depth must lie in [1, 10] (EY_NUTS_MAX_DEPTH)");
+  if (nu.u && nu.S < 1 + 2 * EY_NUTS_MAX_DEPTH + ((int64_t)1 << nu.max_depth))
+    return f.refuse("the uniform table u [C, S] needs S >= 21 + 2^max_depth words");
+  EY_TRY(f.step(step, step_vec));
+  EY_TRY(f.n_iters());
+  EY_TRY(f.factors(G, metric_index));
+  if (pl->da_state)
+    return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which NUTS does not consume; detach it and "
+                    "adapt on the host, or pass the dual averaging as arguments of ey_nuts_warmup");
+  const int n_iters = d.run ? d.run->n_iters : 1;
+  if (da_state && !da_table) return f.refuse("a dual-averaging state (da_state) needs its table (da_table)");
+  if (da_state && !step_vec) return f.refuse("a dual-averaging state (da_state) needs step_vec, the steps it adapts");
+  if (da_state && (da_n < 1 || da_n > n_iters)) return f.refuse("da_n must lie in [1, n_iters]");
+  if (da_state && !std::isfinite(da_d)) return f.refuse("the target acceptance d must be finite");
+  if (!mean != !M2) return f.refuse("mean and M2 go together: exactly one of them is null");
+  if (mean && count < 0) return f.refuse("count must be >= 0");
+  EY_TRY(f.ready(true));
+  EyWarm w;
+  w.da_state = (double*)da_state;
+  w.da_table = (const double*)da_table;
+  w.da_n = da_state ? da_n : 0;
+  w.final_it = da_state && final_avg ? da_n - 1 : -1;
+  w.d = da_d;
+  w.has_eub = log_eub == log_eub ? 1 : 0;  // NaN: no upper bound (ey_plan_attach_da)
+  w.logeub = w.has_eub ? log_eub : 0.0;
+  w.mean = (double*)mean;
+  w.M2 = (double*)M2;
+  w.count = count;
+  w.steps_rec = steps_rec;
+  w.rate_rec = rate_rec;
+  return f.finish(ey_nuts_launch(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, d, nu, w), theta);
+}
+
 static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, const char* who,
                    int transform) {
   EyCall f{pl, d, who};
@@ -1168,6 +1215,46 @@ int ey_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, con
   w.rate_rec = rate_rec;
   return f.finish(ey_generic_hmc_metric_warmup(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, L,
                                                dr, w), theta);
+}
+
+// (declared in include/eeyore_amd_nuts.h)  accept_stat travels as the draw's log_rate: record_draw writes it
+int ey_nuts_step(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                 const void* metric_index, const void* v0, const void* u, int64_t S, double step, const void* step_vec,
+                 int max_depth, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                 uint32_t flags, void* accepted, void* depth, void* n_leapfrog, void* divergent, void* accept_stat,
+                 void* energy, void* stream) {
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, accept_stat, (hipStream_t)stream, nullptr};
+  const EyNuts nu = {v0, u, S, max_depth, (int*)depth, (int*)n_leapfrog, (unsigned char*)divergent, energy, nullptr, nullptr};
+  return nuts_impl(pl, theta, target, grad, metric, form, G, metric_index, step, const_cast<void*>(step_vec), d, nu, nullptr,
+                   nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, 0, nullptr, nullptr, "ey_nuts_step");
+}
+
+int ey_nuts_run(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                const void* metric_index, double step, const void* step_vec, int max_depth, const void* temp, int64_t C,
+                uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                void* targets, void* accepted_rec, void* accept_count, void* accepted, void* depth, void* n_leapfrog,
+                void* divergent, void* accept_stat, void* energy, void* depth_rec, void* divergent_rec, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, accept_stat, (hipStream_t)stream, &run};
+  const EyNuts nu = {nullptr, nullptr, 0, max_depth, (int*)depth, (int*)n_leapfrog, (unsigned char*)divergent, energy,
+                     (int*)depth_rec, (unsigned char*)divergent_rec};
+  return nuts_impl(pl, theta, target, grad, metric, form, G, metric_index, step, const_cast<void*>(step_vec), d, nu, nullptr,
+                   nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, 0, nullptr, nullptr, "ey_nuts_run");
+}
+
+int ey_nuts_warmup(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                   const void* metric_index, double step, void* step_vec, int max_depth, const void* temp, int64_t C,
+                   uint64_t seed, uint64_t iter, uint64_t chain_offset, uint32_t flags, int n_iters, void* samples,
+                   void* targets, void* accepted_rec, void* accept_count, void* accepted, void* depth, void* n_leapfrog,
+                   void* divergent, void* accept_stat, void* energy, void* depth_rec, void* divergent_rec, void* da_state,
+                   const void* da_table, int da_n, double d, double log_eub, int final_avg, void* mean, void* M2,
+                   int64_t count, void* steps_rec, void* rate_rec, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw dr = {temp, C, seed, iter, chain_offset, flags, accepted, accept_stat, (hipStream_t)stream, &run};
+  const EyNuts nu = {nullptr, nullptr, 0, max_depth, (int*)depth, (int*)n_leapfrog, (unsigned char*)divergent, energy,
+                     (int*)depth_rec, (unsigned char*)divergent_rec};
+  return nuts_impl(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, dr, nu, da_state, da_table, da_n,
+                   d, log_eub, final_avg, mean, M2, count, steps_rec, rate_rec, "ey_nuts_warmup");
 }
 
 int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,

@@ -111,6 +111,8 @@ struct ey_plan {
   // whether their LDS limit has been raised
   int* d_mid32_tab = nullptr;
   bool mid32_attr = false, mid_attr = false;
+  // the NUTS kernel (ey_nuts.hip): the instantiation whose LDS limit this plan has raised (to 160 KiB, once)
+  const void* nuts_attr = nullptr;
 };
 
 // The diagnostic switches of the plan a C-ABI call is serving, for the dispatch code below the entry points (thread-local:

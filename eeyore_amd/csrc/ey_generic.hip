@@ -19,6 +19,13 @@
 
 #include "ey_common.h"
 
+// EY_GEN_PART: ey_nuts.hip includes this file with EY_GEN_PART 1 for what its kernel shares with the kernels here (the
+// evaluation, the LDS image, the sweeps and leapfrog halves under a metric, the launch helpers): every entry point, and
+// with them every kernel instantiation of this unit, is then left out.  0 (this file as it stands) = the whole unit.
+#ifndef EY_GEN_PART
+#define EY_GEN_PART 0
+#endif
+
 #define TS 65
 #define WAVE 64
 
@@ -186,7 +193,7 @@ static size_t lds_total(const EyModel& m, int nvec, size_t esz, int nw) {
 // extent with wave-uniform guards, so all register arrays are indexed by constants.
 #define TINY_D0 8
 #define TINY_DH 4
-bool ey_generic_tiny_ok(const EyModel& m) {
+static bool ey_generic_tiny_ok(const EyModel& m) {
   if (m.nl < 1 || m.nl > 3 || m.dims[0] > TINY_D0) return false;
   for (int k = 1; k <= m.nl; ++k)
     if (m.dims[k] > TINY_DH) return false;
@@ -581,10 +588,12 @@ __device__ T mix_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, b
   return val;
 }
 // the scratch of mix_target in units of the carve: hrows rows of TS elements, no delta ping-pong
+#if EY_GEN_PART == 0
 void ey_generic_mix_scratch(EyModel& m) {
   m.hrows = (m.N * m.P + m.P + 2 * m.N + TS - 1) / TS;
   m.dmax = 0;
 }
+#endif
 
 // ------------------------------------------------------------------ exponential-tilt target (EY_KIND_TILT)
 // The reference's Gamma examples sample theta = log x with the Jacobian in the closure; that density and its
@@ -623,10 +632,12 @@ __device__ T tilt_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, 
   return val;
 }
 // ... which has no scratch: no activation rows, no delta ping-pong
+#if EY_GEN_PART == 0
 void ey_generic_tilt_scratch(EyModel& m) {
   m.hrows = 0;
   m.dmax = 0;
 }
+#endif
 
 template <typename T, bool GRAD, class TINY = TinyOff>
 __device__ T eval_target(const EyModel& m, const Lds<T>& l, const T* th, T* gr, bool has_temp, T temp, T* lik_out,
@@ -1238,6 +1249,7 @@ static int launch_row_waves(ey_plan* pl, int nvec, int64_t C, hipStream_t s, KF 
 }
 #define EY_RW_KERNEL(k, ...) [](auto rw_tag) { return k<__VA_ARGS__, decltype(rw_tag)::value>; }
 
+#if EY_GEN_PART == 0
 template <typename T, class TINY>
 static int launch_log_target(ey_plan* pl, const void* theta, const void* temp, int64_t C, void* lik, void* prior,
                              void* target, void* grad, hipStream_t s, void* rows = nullptr) {
@@ -1323,6 +1335,7 @@ int ey_generic_mh(ey_plan* pl, void* theta, void* target, const void* z, const v
                   const EyDraw& d) {
   return EY_TINY_DISPATCH(tiny_dispatch, launch_mh, pl, theta, target, z, u, scale, d);
 }
+#endif  // EY_GEN_PART == 0
 
 // ----------------------------------------------------------------------------------------------- robust adaptive Metropolis
 // RAM.draw (eeyore/samplers/ram.py:38-70; Vihola 2012): propose theta + S z with the chain's lower-triangular factor S,
@@ -1530,6 +1543,7 @@ static int tril_limits(const ey_plan* pl, const std::string& name, const std::st
   return EY_OK;
 }
 
+#if EY_GEN_PART == 0
 template <typename T, class TINY>
 static int launch_ram(ey_plan* pl, void* theta, void* target, void* chol, const void* z, const void* u, double a,
                       double g, uint64_t n, const EyDraw& d) {
@@ -1547,6 +1561,7 @@ int ey_generic_ram(ey_plan* pl, void* theta, void* target, void* chol, const voi
   if (int rc = tril_limits(pl, "RAM", "the factor", "the factor", ey_generic_ram_lds(pl))) return rc;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_ram, pl, theta, target, chol, z, u, a, g, n, d);
 }
+#endif  // EY_GEN_PART == 0
 
 // ----------------------------------------------------------------------------------------------- MH with a fixed factor
 // MetropolisHastings.draw (eeyore/samplers/metropolis_hastings.py:41-73) whose kernel is a MultivariateNormalKernel: the
@@ -1607,6 +1622,7 @@ __global__ void __launch_bounds__(WAVE) k_mh_tril(EyModel m, T* theta, T* target
   }
 }
 
+#if EY_GEN_PART == 0
 template <typename T, class TINY>
 static int launch_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril, int64_t G, const void* tril_index,
                           const void* z, const void* u, const EyDraw& d) {
@@ -1624,6 +1640,7 @@ int ey_generic_mh_tril(ey_plan* pl, void* theta, void* target, const void* tril,
   if (int rc = tril_limits(pl, "MH with a factor", "the factor", "the factor", ey_generic_mh_tril_lds(pl))) return rc;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_mh_tril, pl, theta, target, tril, G, tril_index, z, u, d);
 }
+#endif  // EY_GEN_PART == 0
 
 // ----------------------------------------------------------------------------------------------- MALA with a fixed factor
 // MALA.draw (eeyore/samplers/mala.py:46-82) whose kernel is a MultivariateNormalKernel: the proposal
@@ -1742,6 +1759,7 @@ __global__ void __launch_bounds__(WAVE) k_mala_tril(EyModel m, T* theta, T* targ
   }
 }
 
+#if EY_GEN_PART == 0
 template <typename T, class TINY>
 static int launch_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, const void* tril, int64_t G,
                             const void* tril_index, const void* z, const void* u, double step, const void* step_vec,
@@ -1763,6 +1781,7 @@ int ey_generic_mala_tril(ey_plan* pl, void* theta, void* target, void* grad, con
   return EY_TINY_DISPATCH(tiny_dispatch, launch_mala_tril, pl, theta, target, grad, tril, G, tril_index, z, u, step,
                           step_vec, d);
 }
+#endif  // EY_GEN_PART == 0
 
 // ----------------------------------------------------------------------------------------------- HMC with a fixed metric
 // Euclidean-metric HMC with a fixed inverse metric Sigma = L L^T (Stan's diag_e / dense_e): p ~ N(0, Sigma^-1),
@@ -1832,6 +1851,7 @@ __host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, siz
     }                                                                                   \
   } while (0)
 
+#if EY_GEN_PART == 0  // (to the end of the file)
 template <typename T, class TINY, int FORM>
 __global__ void __launch_bounds__(WAVE) k_hmc_metric(EyModel m, T* theta, T* target, T* grad, const T* metric, int64_t G,
                                                      const int* metric_index, const T* v0, const T* u_in, T step,
@@ -2683,3 +2703,4 @@ int ey_generic_am(ey_plan* pl, void* theta, void* target, const EyAm& am, const 
 bool ey_generic_am_softabs_fits(const ey_plan* pl) {
   return pl->m.P <= RAM_MAX_P && ey_generic_am_lds(pl, EY_AM_SOFTABS) <= 160 * 1024;
 }
+#endif  // EY_GEN_PART == 0

@@ -1,0 +1,25 @@
+// What ey_api.hip and ey_nuts.hip share about the No-U-Turn sampler (include/eeyore_amd_nuts.h).
+#pragma once
+
+#include "../../include/eeyore_amd_nuts.h"
+#include "ey_common.h"
+
+// the arguments of k_nuts beside those of ey_generic_hmc_metric_warmup: parity inputs, the depth cap, the outputs of a draw
+struct EyNuts {
+  const void* v0;  // [C,P] or null
+  const void* u;   // [C,S] or null
+  int64_t S;
+  int max_depth;
+  int* depth;                // [C] or null
+  int* n_leapfrog;           // [C] or null
+  unsigned char* divergent;  // [C] or null
+  void* energy;              // [C] of the plan's dtype, or null (accept_stat travels as EyDraw::log_rate)
+  int* depth_rec;            // [n_iters,C] or null
+  unsigned char* div_rec;    // [n_iters,C] or null
+};
+
+size_t ey_nuts_lds(const ey_plan* pl, int form);  // dynamic LDS of one chain's workgroup
+// the limits (P, LDS), before any launch; then the launch of k_nuts.  step_vec is in/out when w carries a dual averaging.
+int ey_nuts_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
+                   const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
+                   const EyWarm& w);

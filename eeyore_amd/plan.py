@@ -670,6 +670,104 @@ class Plan:
         return self._sample(L.lib().ey_hmc_metric_warmup, C, lead, temp, seed, it, chain_offset, flags, out,
                             n_iters=n_iters, records=(samples, targets, accepted_rec, accept_count), tail=tail)
 
+    # ------------------------------------------------------------------ NUTS under a metric (include/eeyore_amd_nuts.h)
+    def _nuts_args(self, theta, metric, form, index, max_depth, out):
+        """(C, form code, G, index, out) of a NUTS call, checked: the metric as ``_metric`` checks it, at most 128 parameters
+        in either form, ``max_depth`` in [1, 10]; ``out`` gets the [C] outputs of a draw it does not hold yet."""
+        C = self._theta(theta)
+        if self.P > 128:
+            raise ValueError(f"NUTS is limited to 128 parameters (the model has {self.P}): the tree lives in LDS")
+        code, G, index = self._metric(metric, form, index, C)
+        if int(max_depth) != max_depth:
+            raise ValueError(f"max_depth must be an integer in [1, {L.EY_NUTS_MAX_DEPTH}]")  # (the range: the library's)
+        out = {} if out is None else out
+        for name, dt in (("accepted", torch.uint8), ("depth", torch.int32), ("n_leapfrog", torch.int32),
+                         ("divergent", torch.uint8), ("accept_stat", self.dtype), ("energy", self.dtype)):
+            if name not in out:
+                out[name] = self.empty(C, dtype=dt)
+            self._want(name, out[name], (C,), dt)
+        return C, code, G, index, out
+
+    @staticmethod
+    def _nuts_out(out):
+        return tuple(L.ptr(out[k]) for k in ("depth", "n_leapfrog", "divergent", "accept_stat", "energy"))
+
+    def nuts_step(self, theta, target, grad, step, max_depth, metric, form, index=None, v0=None, u=None, step_vec=None,
+                  temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
+        """One draw of multinomial NUTS for every chain under a fixed metric (ey_nuts_step): ``metric``,
+        ``form`` and ``index`` as in ``hmc_metric_step``, at most 128 parameters in either form; ``max_depth`` in [1, 10]
+        doublings.  ``v0`` [C, P] replaces the draw of the whitened velocity, ``u`` [C, S] (S >= 21 + 2^max_depth) the
+        chain's uniform stream in its word layout (1 + 2d the direction of doubling d, 2 + 2d its top-level move, 21 + n
+        leaf n).  Returns accepted (the state moved), depth, n_leapfrog, divergent, accept_stat, energy, each [C]."""
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        step_vec = self._opt(step_vec, C)
+        S = 0
+        if u is not None:
+            if u.dim() != 2:
+                raise ValueError("u must be a [C, S] table of uniforms")
+            S = int(u.shape[1])
+            self._want("u", u, (C, S), self.dtype)
+        if v0 is not None:
+            self._want("v0", v0, (C, self.P), self.dtype)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), L.ptr(v0), L.ptr(u), S,
+                float(step), L.ptr(step_vec), int(max_depth))
+        return self._sample(L.lib().ey_nuts_step, C, lead, temp, seed, it, chain_offset, flags, out,
+                            tail=self._nuts_out(out))
+
+    def _nuts_recs(self, n_iters, C, depth_rec, divergent_rec):
+        for name, t, dt in (("depth_rec", depth_rec, torch.int32), ("divergent_rec", divergent_rec, torch.uint8)):
+            if t is not None:
+                self._want(name, t, (n_iters, C), dt)
+        return L.ptr(depth_rec), L.ptr(divergent_rec)
+
+    def nuts_run(self, theta, target, grad, step, max_depth, metric, form, n_iters, index=None, step_vec=None, temp=None,
+                 seed=0, it=0, chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None,
+                 depth_rec=None, divergent_rec=None, out=None):
+        """``n_iters`` iterations of ``nuts_step`` on the in-kernel streams in one launch (ey_nuts_run), bit for bit;
+        records as in ``hmc_run``, and ``depth_rec`` [n_iters, C] int32, ``divergent_rec`` [n_iters, C] uint8."""
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        step_vec = self._opt(step_vec, C)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), float(step),
+                L.ptr(step_vec), int(max_depth))
+        tail = self._nuts_out(out) + self._nuts_recs(int(n_iters), C, depth_rec, divergent_rec)
+        return self._sample(L.lib().ey_nuts_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count), tail=tail)
+
+    def nuts_warmup(self, theta, target, grad, step, max_depth, metric, form, n_iters, index=None, step_vec=None,
+                    temp=None, seed=0, it=0, chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None,
+                    accept_count=None, depth_rec=None, divergent_rec=None, out=None, da_state=None, da_table=None, d=0.8,
+                    log_eub=None, final_avg=False, mean=None, M2=None, count=0, steps_rec=None, rate_rec=None):
+        """``nuts_run`` with the two epilogues of ``hmc_metric_warmup`` after each draw (ey_nuts_warmup): dual averaging of
+        every chain's step on the draw's accept_stat, Welford moments of the state it is left in.  The arguments from
+        ``da_state`` on are ``hmc_metric_warmup``'s (``rate_rec`` records accept_stat); with none of them it is
+        ``nuts_run``, bit for bit."""
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        n_iters, f64 = int(n_iters), torch.float64
+        if da_state is not None or steps_rec is not None:
+            if step_vec is not None:  # in/out: the caller's own tensor, not a converted copy
+                self._want("step_vec", step_vec, (C,), self.dtype)
+        else:
+            step_vec = self._opt(step_vec, C)
+        if da_state is not None:
+            self._want("da_state", da_state, (C, 3), f64)
+            if da_table is not None:
+                self._want("da_table", da_table, (da_table.shape[0], 3), f64)
+        for name, t, shape in (("mean", mean, (C, self.P)),
+                               ("M2", M2, (C, self.P) if form == "diag" else (C, self.P, self.P))):
+            if t is not None:
+                self._want(name, t, shape, f64)
+        for name, t in (("steps_rec", steps_rec), ("rate_rec", rate_rec)):
+            if t is not None:
+                self._want(name, t, (n_iters, C), self.dtype)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), float(step),
+                L.ptr(step_vec), int(max_depth))
+        tail = self._nuts_out(out) + self._nuts_recs(n_iters, C, depth_rec, divergent_rec) + (
+            L.ptr(da_state), L.ptr(da_table), 0 if da_table is None else int(da_table.shape[0]), float(d),
+            float('nan') if log_eub is None else float(log_eub), int(bool(final_avg)), L.ptr(mean), L.ptr(M2), int(count),
+            L.ptr(steps_rec), L.ptr(rate_rec))
+        return self._sample(L.lib().ey_nuts_warmup, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count), tail=tail)
+
     def metric_from_moments(self, mean, M2, n, form, pooled=True, table=None, status=None):
         """A metric table of the plan's dtype from the running moments ``hmc_metric_warmup`` leaves after ``n`` draws of
         every chain (ey_metric_from_moments): Stan's regularised estimate as ``DiagMetric`` / ``DenseMetric.from_samples``

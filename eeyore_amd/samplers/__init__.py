@@ -1,5 +1,6 @@
 from .base import Sampler, SerialSampler, SingleChainSerialSampler
 from .hmc import HMC
+from .nuts import NUTS
 from .metric import DenseMetric, DiagMetric
 from .mala import MALA
 from .metropolis_hastings import MetropolisHastings

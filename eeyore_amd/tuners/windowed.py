@@ -112,6 +112,9 @@ class WindowedAdaptation(Tuner):
         if plan._moments is not None:  # attached chain moments are replayed from records a burn-in block does not keep
             block = 1
         flags = L.EY_RECOMPUTE_INITIAL_GRAD if sampler.recompute_initial_grad else 0
+        # a sampler with a warm-up launch of its own (NUTS: ey_nuts_warmup) gives it as _warmup_launch(plan, num_steps, k,
+        # **the keywords below); HMC has none and goes through ey_hmc_metric_warmup
+        launch = getattr(sampler, '_warmup_launch', None)
         self.history = []
         step = self.start_steps(sampler, plan, 0)
         state, t = self.restart(step), 1
@@ -122,12 +125,15 @@ class WindowedAdaptation(Tuner):
             while start + done < end:
                 k = min(block, end - start - done)
                 last = start + done + k == n
-                out = plan.hmc_metric_warmup(
-                    sampler._theta, sampler._target, sampler._grad, 0.0, self.fixed_num_steps, sampler._metric, form, k,
-                    index=sampler._metric_index, step_vec=step, temp=sampler._temp(), seed=sampler.seed, it=sampler._iter,
-                    chain_offset=sampler.chain_offset, flags=flags, da_state=state, da_table=self.table(t, k, dev),
-                    d=self.d, log_eub=self.logeub, final_avg=last, mean=mean if adapts else None,
-                    M2=M2 if adapts else None, count=done)
+                kw = dict(index=sampler._metric_index, step_vec=step, temp=sampler._temp(), seed=sampler.seed,
+                          it=sampler._iter, chain_offset=sampler.chain_offset, flags=flags, da_state=state,
+                          da_table=self.table(t, k, dev), d=self.d, log_eub=self.logeub, final_avg=last,
+                          mean=mean if adapts else None, M2=M2 if adapts else None, count=done)
+                if launch is not None:
+                    out = launch(plan, self.fixed_num_steps, k, **kw)
+                else:
+                    out = plan.hmc_metric_warmup(sampler._theta, sampler._target, sampler._grad, 0.0, self.fixed_num_steps,
+                                                 sampler._metric, form, k, **kw)
                 done, t = done + k, t + k
                 sampler._iter += k
                 sampler.last = out
