@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
-include/eeyore_amd_nuts.h).
+include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -128,6 +128,15 @@ NUTS_SYMBOLS = {
                        + [_vp, _vp, _i, _d, _d, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
+# ... and what include/eeyore_amd_eslice.h declares, elliptical slice sampling: a fifth table.  A step takes theta, target,
+# ell, base_loc, base_scale, z, u, S, max_shrinks before _DRAW and accepted, n_evals after it; a run adds n_evals_rec.
+EY_ESLICE_MAX_SHRINKS = 64
+ESLICE_SYMBOLS = {
+    "ey_eslice_ell": (_i, [_vp] * 5 + [_i64] + [_vp] * 3),
+    "ey_eslice_step": (_i, [_vp] * 8 + [_i64, _i] + _DRAW + [_vp] * 3),
+    "ey_eslice_run": (_i, [_vp] * 6 + [_i] + _RUN + [_vp] * 2),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -159,7 +168,7 @@ def lib():
                 "g.build()'` (or `make -C eeyore_amd/csrc`); there is no CPU fallback")
         L = ct.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
-                                  + list(NUTS_SYMBOLS.items())):
+                                  + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

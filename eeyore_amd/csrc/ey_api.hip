@@ -9,6 +9,7 @@
 
 #include "ey_common.h"
 #include "ey_nuts.h"
+#include "ey_eslice.h"
 
 static thread_local std::string g_err;
 void ey_set_error(const std::string& msg) { g_err = msg; }
@@ -1024,6 +1025,37 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
   return f.finish(ey_nuts_launch(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, d, nu, w), theta);
 }
 
+// Elliptical slice sampling (include/eeyore_amd_eslice.h): one kernel of ey_eslice.hip on the generic evaluation for every
+// model, as the samplers above.  What is refused about the base, before anything else is looked at:
+static int eslice_base(const ey_plan* pl, const void* base_loc, const void* base_scale, const char* who) {
+  if (!base_loc != !base_scale)
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": base_loc and base_scale go together: exactly one of them is null");
+  if (!base_loc && is_mix(pl))
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": " + mix_noun(pl) + " has no prior to slice under; give the Gaussian base "
+                                               "(base_loc, base_scale)");
+  if (!base_loc && !prior_normal(pl))
+    EY_FAIL(EY_ERR_INVALID, std::string(who) + ": without a base the plan's prior must be Normal (it is " + prior_name(pl) +
+                                               "); give the Gaussian base (base_loc, base_scale)");
+  return EY_OK;
+}
+
+static int eslice_impl(ey_plan* pl, void* theta, void* target, const EyEslice& es, const EyDraw& d, const char* who) {
+  EyCall f{pl, d, who};
+  if (int rc = f.begin(4)) return done(rc);  // k_eslice carves four state vectors from LDS
+  if (!theta || !target || !es.ell || !d.accepted) return f.refuse("null argument");
+  EY_TRY(eslice_base(pl, es.base_loc, es.base_scale, who));
+  if (es.max_shrinks < 1 || es.max_shrinks > EY_ESLICE_MAX_SHRINKS)
+    return f.refuse("max_shrinks must lie in [1, 64] (EY_ESLICE_MAX_SHRINKS)");
+  if (es.u && es.S < 2 + (int64_t)es.max_shrinks)
+    return f.refuse("the uniform table u [C, S] needs S >= 2 + max_shrinks words");
+  EY_TRY(f.n_iters());
+  if (pl->da_state)
+    return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which elliptical slice sampling does not "
+                    "consume (it has no step); detach it");
+  EY_TRY(f.ready(true));
+  return f.finish(ey_eslice_launch(pl, theta, target, es, d), theta);
+}
+
 static int am_impl(ey_plan* pl, void* theta, void* target, const EyAm& am, const EyDraw& d, const char* who,
                    int transform) {
   EyCall f{pl, d, who};
@@ -1255,6 +1287,36 @@ int ey_nuts_warmup(ey_plan* pl, void* theta, void* target, void* grad, const voi
                      (int*)depth_rec, (unsigned char*)divergent_rec};
   return nuts_impl(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, dr, nu, da_state, da_table, da_n,
                    d, log_eub, final_avg, mean, M2, count, steps_rec, rate_rec, "ey_nuts_warmup");
+}
+
+// (declared in include/eeyore_amd_eslice.h)
+int ey_eslice_ell(ey_plan* pl, const void* theta, const void* base_loc, const void* base_scale, const void* temp, int64_t C,
+                  void* ell, void* target, void* stream) {
+  int rc = check_ready(pl, C, "ey_eslice_ell", 4);
+  if (rc) return rc < 0 ? rc : EY_OK;
+  EyVariantScope vs(pl);
+  if (!theta) EY_FAIL(EY_ERR_INVALID, "ey_eslice_ell: null argument");
+  if ((rc = eslice_base(pl, base_loc, base_scale, "ey_eslice_ell"))) return rc;
+  EY_HIP(hipSetDevice(pl->device));
+  return ey_eslice_ell_launch(pl, theta, base_loc, base_scale, temp, C, ell, target, (hipStream_t)stream);
+}
+
+int ey_eslice_step(ey_plan* pl, void* theta, void* target, void* ell, const void* base_loc, const void* base_scale,
+                   const void* z, const void* u, int64_t S, int max_shrinks, const void* temp, int64_t C, uint64_t seed,
+                   uint64_t iter, uint64_t chain_offset, uint32_t flags, void* accepted, void* n_evals, void* stream) {
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, nullptr};
+  const EyEslice es = {base_loc, base_scale, z, u, S, max_shrinks, ell, (int*)n_evals, nullptr};
+  return eslice_impl(pl, theta, target, es, d, "ey_eslice_step");
+}
+
+int ey_eslice_run(ey_plan* pl, void* theta, void* target, void* ell, const void* base_loc, const void* base_scale,
+                  int max_shrinks, const void* temp, int64_t C, uint64_t seed, uint64_t iter, uint64_t chain_offset,
+                  uint32_t flags, int n_iters, void* samples, void* targets, void* accepted_rec, void* accept_count,
+                  void* accepted, void* n_evals, void* n_evals_rec, void* stream) {
+  const EyRun run = {n_iters, samples, targets, accepted_rec, (int*)accept_count};
+  const EyDraw d = {temp, C, seed, iter, chain_offset, flags, accepted, nullptr, (hipStream_t)stream, &run};
+  const EyEslice es = {base_loc, base_scale, nullptr, nullptr, 0, max_shrinks, ell, (int*)n_evals, (int*)n_evals_rec};
+  return eslice_impl(pl, theta, target, es, d, "ey_eslice_run");
 }
 
 int ey_am_step(ey_plan* pl, void* theta, void* target, void* running_mean, void* cov_sum, void* cov, void* num_accepted,

@@ -768,6 +768,89 @@ class Plan:
         return self._sample(L.lib().ey_nuts_warmup, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
                             records=(samples, targets, accepted_rec, accept_count), tail=tail)
 
+    # ------------------------------------------------------------------ elliptical slice sampling (include/eeyore_amd_eslice.h)
+    def _eslice_base(self, base_loc, base_scale):
+        """The two base tables as [P] tensors of the plan's dtype on its device (or None, None), checked: both or neither,
+        every scale positive and finite (the library sees device pointers only and cannot look)."""
+        if (base_loc is None) != (base_scale is None):
+            raise ValueError("base_loc and base_scale go together: give both tables of the Gaussian base, or neither")
+        if base_loc is None:
+            return None, None
+        seen = getattr(self, '_eslice_seen', None)  # the pair checked last, unmodified: no second look (it synchronises)
+        if (seen is not None and seen[0] is base_loc and seen[1] is base_scale
+                and seen[2] == (base_loc._version, base_scale._version)):
+            return base_loc, base_scale
+        kw = dict(dtype=self.dtype, device=self.device)
+        loc = self._prep(torch.broadcast_to(torch.as_tensor(base_loc, **kw), (self.P,)))
+        scale = self._prep(torch.broadcast_to(torch.as_tensor(base_scale, **kw), (self.P,)))
+        if not bool((torch.isfinite(scale) & (scale > 0)).all()):
+            raise ValueError("base_scale must be positive and finite in every coordinate")
+        if not bool(torch.isfinite(loc).all()):
+            raise ValueError("base_loc must be finite in every coordinate")
+        if loc is base_loc and scale is base_scale:  # already [P] tensors of the plan's: remembered
+            self._eslice_seen = (loc, scale, (loc._version, scale._version))
+        return loc, scale
+
+    def eslice_ell(self, theta, base_loc=None, base_scale=None, temp=None):
+        """(ell [C], target [C]) at ``theta`` (ey_eslice_ell): what elliptical slice sampling slices on -- the (tempered)
+        log-likelihood under the plan's Normal prior, or with a Gaussian base the (tempered) log-target minus the base's
+        exponent -- and the (tempered) log-target, from the value-only evaluation ``eslice_step`` makes."""
+        C = self._theta(theta)
+        loc, scale = self._eslice_base(base_loc, base_scale)
+        ell, target = self.empty(C), self.empty(C)
+        temp = self._opt(temp, C)
+        L.check(L.lib().ey_eslice_ell(self.handle, L.ptr(theta), L.ptr(loc), L.ptr(scale), L.ptr(temp), C, L.ptr(ell),
+                                      L.ptr(target), _stream(self.device)), "ey_eslice_ell")
+        return ell, target
+
+    def _eslice_args(self, theta, target, ell, max_shrinks, out):
+        C = self._theta(theta)
+        self._want("target", target, (C,), self.dtype)
+        self._want("ell", ell, (C,), self.dtype)
+        if int(max_shrinks) != max_shrinks:
+            raise ValueError(f"max_shrinks must be an integer in [1, {L.EY_ESLICE_MAX_SHRINKS}]")  # (the range: the library's)
+        out = {} if out is None else out
+        for name, dt in (("accepted", torch.uint8), ("n_evals", torch.int32)):
+            if name not in out:
+                out[name] = self.empty(C, dtype=dt)
+            self._want(name, out[name], (C,), dt)
+        return C, out
+
+    def eslice_step(self, theta, target, ell, base_loc=None, base_scale=None, z=None, u=None, max_shrinks=64, temp=None,
+                    seed=0, it=0, chain_offset=0, flags=0, out=None):
+        """One elliptical slice draw of every chain (ey_eslice_step), in place on ``theta`` [C, P],
+        ``target`` [C] and ``ell`` [C] (as ``eslice_ell`` returns them).  Without a base the plan's Normal prior is the
+        Gaussian and ell the log-likelihood; ``base_loc`` / ``base_scale`` [P] name another.  ``z`` [C, P] replaces the
+        chain's normal stream, ``u`` [C, S] (S >= 2 + max_shrinks) its uniform stream in the word layout (0 the slice
+        height, 1 the first angle, 2 + k the k-th shrink).  Returns accepted (the chain moved) and n_evals, each [C]."""
+        C, out = self._eslice_args(theta, target, ell, max_shrinks, out)
+        loc, scale = self._eslice_base(base_loc, base_scale)
+        S = 0
+        if u is not None:
+            if u.dim() != 2:
+                raise ValueError("u must be a [C, S] table of uniforms")
+            S = int(u.shape[1])
+            self._want("u", u, (C, S), self.dtype)
+        if z is not None:
+            self._want("z", z, (C, self.P), self.dtype)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(ell), L.ptr(loc), L.ptr(scale), L.ptr(z), L.ptr(u), S, int(max_shrinks))
+        return self._sample(L.lib().ey_eslice_step, C, lead, temp, seed, it, chain_offset, flags, out,
+                            tail=(L.ptr(out["n_evals"]),))
+
+    def eslice_run(self, theta, target, ell, n_iters, base_loc=None, base_scale=None, max_shrinks=64, temp=None, seed=0,
+                   it=0, chain_offset=0, flags=0, samples=None, targets=None, accepted_rec=None, accept_count=None,
+                   n_evals_rec=None, out=None):
+        """``n_iters`` iterations of ``eslice_step`` on the in-kernel streams in one launch (ey_eslice_run), bit for bit;
+        records as in ``mh_run``, and ``n_evals_rec`` [n_iters, C] int32."""
+        C, out = self._eslice_args(theta, target, ell, max_shrinks, out)
+        loc, scale = self._eslice_base(base_loc, base_scale)
+        if n_evals_rec is not None:
+            self._want("n_evals_rec", n_evals_rec, (int(n_iters), C), torch.int32)
+        lead = (L.ptr(theta), L.ptr(target), L.ptr(ell), L.ptr(loc), L.ptr(scale), int(max_shrinks))
+        return self._sample(L.lib().ey_eslice_run, C, lead, temp, seed, it, chain_offset, flags, out, n_iters=n_iters,
+                            records=(samples, targets, accepted_rec, accept_count),
+                            tail=(L.ptr(out["n_evals"]), L.ptr(n_evals_rec)))
+
     def metric_from_moments(self, mean, M2, n, form, pooled=True, table=None, status=None):
         """A metric table of the plan's dtype from the running moments ``hmc_metric_warmup`` leaves after ``n`` draws of
         every chain (ey_metric_from_moments): Stan's regularised estimate as ``DiagMetric`` / ``DenseMetric.from_samples``

@@ -8,3 +8,4 @@ from .power_posterior_sampler import PowerPosteriorSampler
 from .ram import RAM
 from .gibbs import Gibbs
 from .am import AM, Ridge, SoftAbs
+from .elliptical_slice import EllipticalSlice
