@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
-include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h).
+include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h, include/eeyore_amd_eslice_fused.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -137,6 +137,12 @@ ESLICE_SYMBOLS = {
     "ey_eslice_run": (_i, [_vp] * 6 + [_i] + _RUN + [_vp] * 2),
 }
 
+# ... and what include/eeyore_amd_eslice_fused.h declares, a sixth table: which kernel serves elliptical slice sampling on a
+# plan under given flags, b"mfma32" (the fused form on the matrix cores) or b"generic"
+ESLICE_FUSED_SYMBOLS = {
+    "ey_eslice_kernel": (ct.c_char_p, [_vp, _u32]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -168,7 +174,8 @@ def lib():
                 "g.build()'` (or `make -C eeyore_amd/csrc`); there is no CPU fallback")
         L = ct.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
-                                  + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())):
+                                  + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())
+                                  + list(ESLICE_FUSED_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -1026,7 +1026,9 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
 }
 
 // Elliptical slice sampling (include/eeyore_amd_eslice.h): one kernel of ey_eslice.hip on the generic evaluation for every
-// model, as the samplers above.  What is refused about the base, before anything else is looked at:
+// model, as the samplers above -- and, for the plans the mfma32 family serves, its fused form on the matrix cores
+// (ey_eslice_mfma.hip) unless the call asks for the generic kernels.  Every refusal is the same on both and
+// fires before the choice.  What is refused about the base, before anything else is looked at:
 static int eslice_base(const ey_plan* pl, const void* base_loc, const void* base_scale, const char* who) {
   if (!base_loc != !base_scale)
     EY_FAIL(EY_ERR_INVALID, std::string(who) + ": base_loc and base_scale go together: exactly one of them is null");
@@ -1038,6 +1040,9 @@ static int eslice_base(const ey_plan* pl, const void* base_loc, const void* base
                                                "); give the Gaussian base (base_loc, base_scale)");
   return EY_OK;
 }
+
+// the fused form serves the call (under the plan's variant scope: use_mfma32 reads it)
+static bool eslice_fused(const ey_plan* pl, uint32_t flags) { return use_mfma32(pl) && !(flags & EY_FORCE_GENERIC); }
 
 static int eslice_impl(ey_plan* pl, void* theta, void* target, const EyEslice& es, const EyDraw& d, const char* who) {
   EyCall f{pl, d, who};
@@ -1053,6 +1058,9 @@ static int eslice_impl(ey_plan* pl, void* theta, void* target, const EyEslice& e
     return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which elliptical slice sampling does not "
                     "consume (it has no step); detach it");
   EY_TRY(f.ready(true));
+  // (the generic kernel's LDS limit, checked in ey_eslice_launch, cannot bind on a plan of the mfma32 family: P <= 1315;
+  // the fused kernel's tile and LDS limits are those use_mfma32 has enforced.  Moments are replayed from the records.)
+  if (eslice_fused(pl, d.flags)) return f.finish(ey_eslice_mfma_launch(pl, theta, target, es, d), theta);
   return f.finish(ey_eslice_launch(pl, theta, target, es, d), theta);
 }
 
@@ -1298,7 +1306,16 @@ int ey_eslice_ell(ey_plan* pl, const void* theta, const void* base_loc, const vo
   if (!theta) EY_FAIL(EY_ERR_INVALID, "ey_eslice_ell: null argument");
   if ((rc = eslice_base(pl, base_loc, base_scale, "ey_eslice_ell"))) return rc;
   EY_HIP(hipSetDevice(pl->device));
+  // no flags here: the plan alone decides, so a carried ell comes from the kernel a plain step compares it in
+  if (eslice_fused(pl, 0)) return ey_eslice_mfma_ell_launch(pl, theta, base_loc, base_scale, temp, C, ell, target, (hipStream_t)stream);
   return ey_eslice_ell_launch(pl, theta, base_loc, base_scale, temp, C, ell, target, (hipStream_t)stream);
+}
+
+// (declared in include/eeyore_amd_eslice_fused.h)
+const char* ey_eslice_kernel(const ey_plan* pl, uint32_t flags) {
+  if (!pl || is_mix(pl)) return "generic";
+  EyVariantScope vs(pl);
+  return eslice_fused(pl, flags) ? "mfma32" : "generic";
 }
 
 int ey_eslice_step(ey_plan* pl, void* theta, void* target, void* ell, const void* base_loc, const void* base_scale,

@@ -187,6 +187,11 @@ __device__ __forceinline__ float hsum(float v) {
 #define g_ey_dbg g_ey_dbg_p
 #define g_ey_wave_t g_ey_wave_t_p
 #endif
+#if defined(EY_MF_PART) && EY_MF_PART == 2  // ... and so does ey_eslice_mfma.hip's
+#define g_ey_phase g_ey_phase_e
+#define g_ey_dbg g_ey_dbg_e
+#define g_ey_wave_t g_ey_wave_t_e
+#endif
 __device__ unsigned long long g_ey_phase[32];
 __device__ int g_ey_dbg[64];
 __device__ unsigned long long g_ey_wave_t[3 * 8192];  // per chain: kernel entry, wave start, wave end (s_memrealtime)
@@ -1823,6 +1828,8 @@ __global__ void __launch_bounds__(256, 1) k_mfma32p(MfArgs A) {
 #define EY_MF_PART 0
 #endif
 #define MF_PIPE_TILES 8   // the pipelined form's per-wave regions (4 x 34.3 KB) leave room for 8 row tiles (N <= 256)
+// EY_MF_PART 2 (ey_eslice_mfma.hip: elliptical slice sampling on the device code above): no entry point and no kernel
+// instantiation of this file, only the LDS sizes its launches share.
 // (defined in the translation unit of its own, ey_mfma32p.hip = this file with EY_MF_PART 1: built without packed f32
 // instructions, which never issue in the shadow of a bf16 MFMA)
 int ey_mfma32p_hmc(MfArgs& a, int n_cu, hipStream_t s);
@@ -1857,6 +1864,7 @@ extern "C" int ey_debug_phase_read_p(unsigned long long* out16, int reset) {
 // ----------------------------------------------------------------------------------------------- host side
 // 1: the headline model (both product forms); 2: a 4-32-32 model with another hidden activation or the BCE head, served
 // in the bf16x3 form only (the exact form of those is fused16's); 0: not this kernel's
+#if EY_MF_PART != 2
 int ey_mfma32_kind(const ey_plan* pl) {
   const EyModel& m = pl->m;
   if (pl->dtype != EY_F32 || m.nl != 3) return 0;
@@ -1868,6 +1876,7 @@ int ey_mfma32_kind(const ey_plan* pl) {
   return 0;
 }
 bool ey_mfma32_supports(const ey_plan* pl) { return ey_mfma32_kind(pl) != 0; }
+#endif
 
 static size_t mf_lds_bytes(int ntiles, int waves, int park, int bf3) {
   return sizeof(float) * ((size_t)ntiles * XTILE_FLOATS + (size_t)waves * (WAVE_FLOATS_OF(bf3) + 64 * park)) +
@@ -1878,6 +1887,7 @@ static size_t mf_lds_bytes(int ntiles, int waves, int park, int bf3) {
 #define MF_PARK 12        // position elements parked in LDS during the tile loop ...
 #define MF_PARK_TILES 6   // ... when the data image leaves room for it (N <= 192 rows)
 
+#if EY_MF_PART != 2
 // kernel variant (A/B knob): bit 0 = former launch shape (4-wave workgroups, one chain per wave), bit 1 = no priority
 // balancing between the two waves of a SIMD, bit 2 = no momentum parking (exact form) / no piece
 // images (bf16x3 form: BF3 = 1 where BF3 = 2 would serve), bit 4 = route f32 plans through the layerwise
@@ -2108,4 +2118,5 @@ extern "C" int ey_debug_phase_read(unsigned long long* out16, int reset) {
   return 0;
 }
 #endif
+#endif  // EY_MF_PART != 2
 #endif  // EY_MF_PART

@@ -791,6 +791,13 @@ class Plan:
             self._eslice_seen = (loc, scale, (loc._version, scale._version))
         return loc, scale
 
+    def eslice_kernel(self, flags=0):
+        """'mfma32' or 'generic' (ey_eslice_kernel, include/eeyore_amd_eslice_fused.h): the kernel ``eslice_step`` and
+        ``eslice_run`` take on this plan under ``flags`` -- the fused form on the matrix cores wherever ``kernel`` is
+        'mfma32' (DESIGN.md 4.26), unless ``flags`` holds EY_FORCE_GENERIC.  ``eslice_ell`` takes no flags and follows the
+        plan alone."""
+        return L.lib().ey_eslice_kernel(self.handle, int(flags)).decode()
+
     def eslice_ell(self, theta, base_loc=None, base_scale=None, temp=None):
         """(ell [C], target [C]) at ``theta`` (ey_eslice_ell): what elliptical slice sampling slices on -- the (tempered)
         log-likelihood under the plan's Normal prior, or with a Gaussian base the (tempered) log-target minus the base's

@@ -5,12 +5,19 @@ kernels plus passes over [P], so the ratio of the two should be near 1.
 
     python tools/bench_eslice.py [--chains 4096] [--draws 64] [--repeats 5] [--window 0.25] > profiles/eslice_bench.txt
 
-Plans: the headline model MLP(4-32-32-3) on the iris-shaped batch in f32 (plan.kernel 'mfma32': the sampler runs on the
-generic evaluation all the same); MLP(2-2-1) on XOR (the register-resident evaluation); a linear regression of dims [12, 1]
+Plans: the headline model MLP(4-32-32-3) on the iris-shaped batch in f32 (plan.kernel 'mfma32': since DESIGN.md 4.26 the
+sampler runs on the matrix cores there -- profiles/eslice_bench.txt was taken on the generic evaluation, see ``--fused``); MLP(2-2-1) on XOR (the register-resident evaluation); a linear regression of dims [12, 1]
 on 70 rows (the LDS tile loop); a 32-parameter normal with a base 1.5 times its marginal scale.  Chains start from draws of
 the base.  Times are device events around a window of launches of ``--draws`` draws each, back to back and about
 ``--window`` seconds long, after warm-up launches; the median of ``--repeats`` windows, every launch going on from the state
-the one before left; the two samplers alternate window by window."""
+the one before left; the two samplers alternate window by window.
+
+    python tools/bench_eslice.py --fused [...] > profiles/eslice_fused_bench.txt
+
+The headline plan alone, three figures from one process: the time per evaluation of the fused kernel on the
+matrix cores (k_eslice_mfma), the same under EY_FORCE_GENERIC (k_eslice), and ``ey_mh_run``'s time per draw on the matrix
+cores -- one value-only fused evaluation per draw, what a point of the ellipse costs at best.  The three alternate window
+by window; each path goes on from its own state."""
 import argparse
 import os
 import statistics
@@ -70,13 +77,77 @@ def timed(fn):
     return a.elapsed_time(b) * 1e-3
 
 
+def fused(a):
+    """The headline plan: fused, forced generic, ey_mh_run."""
+    C, K = a.chains, a.draws
+    name, pl, _, start = next(plans())
+    assert pl.kernel == "mfma32" and pl.eslice_kernel() == "mfma32" and pl.eslice_kernel(L.EY_FORCE_GENERIC) == "generic"
+    gen = torch.Generator().manual_seed(1)
+    th0 = (torch.randn(C, pl.P, generator=gen) * start).to(DEV).contiguous()
+    state = {}
+    for key in ("fused", "generic"):
+        th = th0.clone()
+        ell, tv = pl.eslice_ell(th)
+        state[key] = (th, tv.contiguous(), ell.contiguous(), torch.zeros(K, C, dtype=torch.int32, device=DEV))
+    th2 = th0.clone()
+    lik, prior = pl.log_target(th2)
+    tv2 = (lik + prior).contiguous()
+    it = [0]
+
+    def es(key):
+        th, tv, ell, rec = state[key]
+        return lambda: pl.eslice_run(th, tv, ell, K, seed=3, it=it[0], n_evals_rec=rec,
+                                     flags=L.EY_FORCE_GENERIC if key == "generic" else 0)
+
+    def mh():
+        pl.mh_run(th2, tv2, 0.02, K, seed=3, it=it[0])
+    runs = dict(fused=es("fused"), generic=es("generic"), mh=mh)
+    n = {}
+    for key, fn in runs.items():   # warm-up, and the launches of a window
+        fn()
+        torch.cuda.synchronize()
+        n[key] = max(1, min(512, int(a.window / max(timed(fn), 1e-5))))
+    times = {key: [] for key in runs}
+    means = {key: [] for key in ("fused", "generic")}
+    maxes = {key: [] for key in ("fused", "generic")}
+    for r in range(a.repeats):
+        for key, fn in runs.items():
+            def window():
+                for _ in range(n[key]):
+                    fn()
+                    it[0] += K
+            times[key].append(timed(window) / n[key])
+            if key in means:
+                means[key].append(float(state[key][3].double().mean()))
+                maxes[key].append(int(state[key][3].max()))
+    print(f"# tools/bench_eslice.py --fused: {name}, {C} chains, {K} draws per launch, median of {a.repeats} windows of about "
+          f"{a.window} s, the three paths alternating; {torch.cuda.get_device_name(0)}")
+    print("# path | kernel | draws/s x chains | evaluations per draw: mean, max | time per evaluation (all chains)")
+    per = {}
+    for key in ("fused", "generic"):
+        sec, mean = statistics.median(times[key]), statistics.median(means[key])
+        per[key] = sec / (K * mean)
+        kern = pl.eslice_kernel(L.EY_FORCE_GENERIC if key == "generic" else 0)
+        print(f"eslice_run {key} | {kern} | {C * K / sec:.4e} | {mean:.2f}, {max(maxes[key])} | {per[key] * 1e6:.2f} us   "
+              f"({n[key]} launches a window; per launch: {', '.join(f'{t * 1e3:.3f}' for t in times[key])} ms)")
+    per_mh = statistics.median(times["mh"]) / K
+    print(f"mh_run | {pl.kernel} | {C * K / (per_mh * K):.4e} | 1 | {per_mh * 1e6:.2f} us per draw   "
+          f"({n['mh']} launches a window; per launch: {', '.join(f'{t * 1e3:.3f}' for t in times['mh'])} ms)")
+    print(f"fused / generic, per evaluation: {per['fused'] / per['generic']:.3f}   (generic / fused: {per['generic'] / per['fused']:.2f} x)")
+    print(f"fused evaluation / mh_run draw: {per['fused'] / per_mh:.2f}")
+    return 0 if per["fused"] < per["generic"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fused", action="store_true", help="the headline plan: fused, forced generic and ey_mh_run")
     ap.add_argument("--chains", type=int, default=4096)
     ap.add_argument("--draws", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25)
     a = ap.parse_args()
+    if a.fused:
+        sys.exit(fused(a))
     C, K = a.chains, a.draws
     print(f"# tools/bench_eslice.py: {C} chains, {K} draws per launch, median of {a.repeats} windows of about {a.window} s; "
           f"{torch.cuda.get_device_name(0)}")
