@@ -1800,7 +1800,21 @@ __host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, siz
 }
 
 // The two halves of a leapfrog step under the metric, written once for both forms.  Each ends with the barrier that lets
-// every lane read what the others wrote (a sweep reads the whole of the other vector).
+// every lane read what the others wrote (a sweep reads the whole of the other vector).  The diagonal form's element loops
+// run, in this unit, a trip count that is stated to be wave-uniform (readfirstlane), over the index clamped as in
+// EY_LANE_PASS: as `for (i = lane; i < P; i += WAVE)`, and as EY_LANE_PASS on a P the compiler keeps in a vector register,
+// the loop is left with EXEC empty, and k_hmc_metric<float, TinyDyn, EY_METRIC_DIAG> was built with the copies that carry
+// the image's offsets around the leapfrog loop inside that region, where they copy nothing -- an accepted draw then stored
+// its gradient from the wrong LDS address.  k_nuts (EY_GEN_PART 1) keeps the plain loop: with a lane pass
+// the compiler stops on that unit ("Illegal instruction detected: Operand has incorrect register class"), and
+// tests/test_cross_metric_gpu.py holds its build as it is.
+#if EY_GEN_PART == 0
+#define EY_METRIC_EACH(i)                                                                                         \
+  for (int ey_r_ = 0, ey_nr_ = __builtin_amdgcn_readfirstlane((P + WAVE - 1) / WAVE), i = lane < P ? lane : P - 1; \
+       ey_r_ < ey_nr_; ++ey_r_, i = lane + ey_r_ * WAVE < P ? lane + ey_r_ * WAVE : P - 1)
+#else
+#define EY_METRIC_EACH(i) for (int i = lane, ey_r_ = 0; i < P; i += WAVE)
+#endif
 // v += w L^T g.  Reads: T, FORM, P, R, lane, S, sd, v, l.
 #define EY_METRIC_KICK(w)                                                                   \
   do {                                                                                      \
@@ -1816,7 +1830,10 @@ __host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, siz
         v[lane + r * WAVE < P ? lane + r * WAVE : P - 1] = acc[r];                          \
       }                                                                                     \
     } else {                                                                                \
-      for (int i = lane; i < P; i += WAVE) v[i] = v[i] + (ey_w_ * sd[i]) * l.gr[i];         \
+      EY_METRIC_EACH(i) {                                                                   \
+        (void)ey_r_;                                                                        \
+        v[i] = v[i] + (ey_w_ * sd[i]) * l.gr[i];                                            \
+      }                                                                                     \
     }                                                                                       \
     __syncthreads();                                                                        \
   } while (0)
@@ -1834,7 +1851,10 @@ __host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, siz
         if (i < P) l.th[i] = acc[r];                                                        \
       }                                                                                     \
     } else {                                                                                \
-      for (int i = lane; i < P; i += WAVE) l.th[i] = l.th[i] + (eps * sd[i]) * v[i];        \
+      EY_METRIC_EACH(i) {                                                                   \
+        (void)ey_r_;                                                                        \
+        l.th[i] = l.th[i] + (eps * sd[i]) * v[i];                                           \
+      }                                                                                     \
     }                                                                                       \
     __syncthreads();                                                                        \
   } while (0)

@@ -53,16 +53,18 @@ def given_base(target, m, s):
 
 def draw(f, theta, ell, target, m, s, z, u, max_shrinks=MAX_SHRINKS):
     """One draw of one chain.  ``f(theta) -> (ell, target)``; theta, m, s, z [P]; u [>= 2 + max_shrinks].  Returns
-    dict(theta, ell, target, accepted, n_evals, margin, exhausted, neg, pos): the state the chain is left in, whether it
-    moved, the evaluations made, the draw's margin, and the shrinks made at a negative / a positive angle."""
+    dict(theta, ell, target, accepted, n_evals, margin, exhausted, neg, pos, margin_ell, margin_angle, logy): the state the
+    chain is left in, whether it moved, the evaluations made, the draw's margin, the shrinks made at a negative / a positive
+    angle, the two parts of the margin (the smallest |ell' - log y|, the smallest |a| branched on) and log y."""
     assert 1 <= max_shrinks <= MAX_SHRINKS and len(u) >= words(max_shrinks)
     out = dict(theta=np.array(theta, np.float64), ell=ell, target=target, accepted=False, n_evals=0, margin=np.inf,
-               exhausted=False, neg=0, pos=0)
+               exhausted=False, neg=0, pos=0, margin_ell=np.inf, margin_angle=np.inf, logy=np.nan)
     if not np.isfinite(ell):   # 5. stays put without evaluating
         return out
     nu, x = s * z, theta - m
     with np.errstate(divide="ignore"):
         logy = ell + np.log(u[0])
+    out["logy"] = logy
     a = u[1]
     lo, hi = a - 1.0, a
     k = 0
@@ -71,14 +73,16 @@ def draw(f, theta, ell, target, m, s, z, u, max_shrinks=MAX_SHRINKS):
         th = m + x * c + nu * sn
         e, t = f(th)
         out["n_evals"] += 1
-        if abs(e - logy) < out["margin"]:
-            out["margin"] = abs(e - logy)
+        if abs(e - logy) < out["margin_ell"]:
+            out["margin_ell"] = abs(e - logy)
+        out["margin"] = min(out["margin"], out["margin_ell"])
         if e > logy:   # (a NaN compares false)
             out.update(theta=th, ell=e, target=t, accepted=True)
             return out
         if k == max_shrinks:
             out["exhausted"] = True
             return out
+        out["margin_angle"] = min(out["margin_angle"], abs(a))
         out["margin"] = min(out["margin"], abs(a))
         if a < 0:
             lo, out["neg"] = a, out["neg"] + 1
@@ -88,7 +92,8 @@ def draw(f, theta, ell, target, m, s, z, u, max_shrinks=MAX_SHRINKS):
         k += 1
 
 
-KEYS = ("theta", "ell", "target", "accepted", "n_evals", "margin", "exhausted", "neg", "pos")
+KEYS = ("theta", "ell", "target", "accepted", "n_evals", "margin", "exhausted", "neg", "pos", "margin_ell",
+        "margin_angle", "logy")
 
 
 def draw_chains(fs, theta, ell, target, m, s, z, u, max_shrinks=MAX_SHRINKS):
