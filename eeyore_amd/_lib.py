@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
-include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h, include/eeyore_amd_eslice_fused.h).
+include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h, include/eeyore_amd_eslice_fused.h,
+include/eeyore_amd_nuts_tree.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -143,6 +144,14 @@ ESLICE_FUSED_SYMBOLS = {
     "ey_eslice_kernel": (ct.c_char_p, [_vp, _u32]),
 }
 
+# ... and what include/eeyore_amd_nuts_tree.h declares, a seventh table: the tree of NUTS in a device workspace.
+# EY_NUTS_TREE_DEVICE is a bit of the flags of the three NUTS entry points.
+EY_NUTS_TREE_DEVICE = 8
+NUTS_TREE_SYMBOLS = {
+    "ey_nuts_tree_bytes": (_i64, [_vp, _i64, _i]),
+    "ey_plan_attach_nuts_tree": (_i, [_vp, _vp, _i64]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -175,7 +184,7 @@ def lib():
         L = ct.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
                                   + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())
-                                  + list(ESLICE_FUSED_SYMBOLS.items())):
+                                  + list(ESLICE_FUSED_SYMBOLS.items()) + list(NUTS_TREE_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

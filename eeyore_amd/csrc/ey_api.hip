@@ -1008,6 +1008,18 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
   if (da_state && !std::isfinite(da_d)) return f.refuse("the target acceptance d must be finite");
   if (!mean != !M2) return f.refuse("mean and M2 go together: exactly one of them is null");
   if (mean && count < 0) return f.refuse("count must be >= 0");
+  // the tree in device memory (include/eeyore_amd_nuts_tree.h): an undersized workspace would be stores out of bounds
+  const bool tree_ws = (d.flags & EY_NUTS_TREE_DEVICE) != 0;
+  if (tree_ws) {
+    if (form != EY_METRIC_DIAG)
+      return f.refuse("EY_NUTS_TREE_DEVICE serves the diagonal metric only (form EY_METRIC_DIAG)");
+    if (!pl->nuts_tree)
+      return f.refuse("EY_NUTS_TREE_DEVICE needs a workspace for the tree (ey_plan_attach_nuts_tree)");
+    const int64_t need = ey_nuts_ws_bytes(pl, d.C, nu.max_depth);
+    if (pl->nuts_tree_bytes < need)
+      return f.refuse(("the attached workspace of " + std::to_string(pl->nuts_tree_bytes) + " bytes is smaller than the " +
+                       std::to_string(need) + " bytes the tree of this call needs (ey_nuts_tree_bytes)").c_str());
+  }
   EY_TRY(f.ready(true));
   EyWarm w;
   w.da_state = (double*)da_state;
@@ -1022,6 +1034,8 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
   w.count = count;
   w.steps_rec = steps_rec;
   w.rate_rec = rate_rec;
+  if (tree_ws)
+    return f.finish(ey_nuts_ws_launch(pl, theta, target, grad, metric, G, metric_index, step, step_vec, d, nu, w), theta);
   return f.finish(ey_nuts_launch(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, d, nu, w), theta);
 }
 
@@ -1778,6 +1792,30 @@ extern "C" int ey_plan_attach_da(ey_plan* pl, void* state, void* step_vec, const
   pl->da_has_eub = log_eub == log_eub;  // NaN = no upper bound
   pl->da_logeub = pl->da_has_eub ? log_eub : 0.0;
   pl->da_final_avg = final_avg != 0;
+  return EY_OK;
+}
+
+// (declared in include/eeyore_amd_nuts_tree.h)
+extern "C" int64_t ey_nuts_tree_bytes(const ey_plan* pl, int64_t C, int max_depth) {
+  if (!pl) EY_FAIL(EY_ERR_INVALID, "ey_nuts_tree_bytes: null plan");
+  if (C < 0) EY_FAIL(EY_ERR_INVALID, "ey_nuts_tree_bytes: C must be >= 0");
+  if (max_depth < 1 || max_depth > EY_NUTS_MAX_DEPTH)
+    EY_FAIL(EY_ERR_INVALID, "ey_nuts_tree_bytes: max_depth must lie in [1, 10] (EY_NUTS_MAX_DEPTH)");
+  return ey_nuts_ws_bytes(pl, C, max_depth);
+}
+
+extern "C" int ey_plan_attach_nuts_tree(ey_plan* pl, void* ws, int64_t bytes) {
+  if (!pl) EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_nuts_tree: null plan");
+  if (!ws) {
+    pl->nuts_tree = nullptr;
+    pl->nuts_tree_bytes = 0;
+    return EY_OK;
+  }
+  if (bytes <= 0) EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_nuts_tree: a workspace needs bytes > 0");
+  if ((uintptr_t)ws % (pl->dtype == EY_F32 ? 4 : 8))
+    EY_FAIL(EY_ERR_INVALID, "ey_plan_attach_nuts_tree: the workspace must be aligned to the plan's dtype");
+  pl->nuts_tree = ws;
+  pl->nuts_tree_bytes = bytes;
   return EY_OK;
 }
 

@@ -113,6 +113,11 @@ struct ey_plan {
   bool mid32_attr = false, mid_attr = false;
   // the NUTS kernel (ey_nuts.hip): the instantiation whose LDS limit this plan has raised (to 160 KiB, once)
   const void* nuts_attr = nullptr;
+  // ... and the tree of k_nuts_ws (ey_nuts_ws.hip) in device memory, attached with ey_plan_attach_nuts_tree (caller-owned),
+  // with that kernel's own raised instantiation
+  void* nuts_tree = nullptr;
+  int64_t nuts_tree_bytes = 0;
+  const void* nuts_ws_attr = nullptr;
 };
 
 // The diagnostic switches of the plan a C-ABI call is serving, for the dispatch code below the entry points (thread-local:

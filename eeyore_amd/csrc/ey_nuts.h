@@ -1,7 +1,8 @@
-// What ey_api.hip and ey_nuts.hip share about the No-U-Turn sampler (include/eeyore_amd_nuts.h).
+// What ey_api.hip, ey_nuts.hip and ey_nuts_ws.hip share about the No-U-Turn sampler (include/eeyore_amd_nuts.h,
+// include/eeyore_amd_nuts_tree.h).
 #pragma once
 
-#include "../../include/eeyore_amd_nuts.h"
+#include "../../include/eeyore_amd_nuts_tree.h"  // includes eeyore_amd_nuts.h and the other five
 #include "ey_common.h"
 
 // the arguments of k_nuts beside those of ey_generic_hmc_metric_warmup: parity inputs, the depth cap, the outputs of a draw
@@ -23,3 +24,10 @@ size_t ey_nuts_lds(const ey_plan* pl, int form);  // dynamic LDS of one chain's 
 int ey_nuts_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
                    const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
                    const EyWarm& w);
+
+// k_nuts_ws (ey_nuts_ws.hip): the diagonal form with the tree in the plan's attached workspace (ey_plan::nuts_tree), any P
+// the evaluation image holds.  The bytes of the workspace for C chains at max_depth; the LDS limit, then the launch.
+int64_t ey_nuts_ws_bytes(const ey_plan* pl, int64_t C, int max_depth);
+int ey_nuts_ws_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int64_t G,
+                      const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
+                      const EyWarm& w);

@@ -671,11 +671,36 @@ class Plan:
                             n_iters=n_iters, records=(samples, targets, accepted_rec, accept_count), tail=tail)
 
     # ------------------------------------------------------------------ NUTS under a metric (include/eeyore_amd_nuts.h)
-    def _nuts_args(self, theta, metric, form, index, max_depth, out):
+    def nuts_tree_bytes(self, C, max_depth):
+        """The bytes of the tree's workspace for ``C`` chains at ``max_depth`` (ey_nuts_tree_bytes,
+        include/eeyore_amd_nuts_tree.h): C (12 + 2 max_depth) vectors of P rounded up to 64 elements of the plan's dtype."""
+        n = L.lib().ey_nuts_tree_bytes(self.handle, int(C), int(max_depth))
+        if n < 0:
+            L.check(int(n), "ey_nuts_tree_bytes")
+        return int(n)
+
+    def attach_nuts_tree(self, C, max_depth):
+        """Gives the plan a workspace for the trees of ``C`` chains at ``max_depth`` (ey_plan_attach_nuts_tree), which the
+        NUTS calls with ``flags`` | EY_NUTS_TREE_DEVICE run in: a uint8 tensor the plan keeps referenced.  It grows to the
+        largest request and never shrinks; what it holds is of no account.  Returns the tensor."""
+        need = self.nuts_tree_bytes(C, max_depth)
+        ws = getattr(self, "_nuts_tree", None)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            L.check(L.lib().ey_plan_attach_nuts_tree(self.handle, L.ptr(ws), ws.numel()), "ey_plan_attach_nuts_tree")
+            self._nuts_tree = ws  # keeps the memory alive (and lets the old one go only now)
+        return ws
+
+    def detach_nuts_tree(self):
+        L.check(L.lib().ey_plan_attach_nuts_tree(self.handle, None, 0), "ey_plan_attach_nuts_tree")
+        self._nuts_tree = None
+
+    def _nuts_args(self, theta, metric, form, index, max_depth, out, flags=0):
         """(C, form code, G, index, out) of a NUTS call, checked: the metric as ``_metric`` checks it, at most 128 parameters
-        in either form, ``max_depth`` in [1, 10]; ``out`` gets the [C] outputs of a draw it does not hold yet."""
+        in either form -- unless ``flags`` carry EY_NUTS_TREE_DEVICE and the form is 'diag' (the tree in the attached
+        workspace) --, ``max_depth`` in [1, 10]; ``out`` gets the [C] outputs of a draw it does not hold yet."""
         C = self._theta(theta)
-        if self.P > 128:
+        if self.P > 128 and not (int(flags) & L.EY_NUTS_TREE_DEVICE and form == "diag"):
             raise ValueError(f"NUTS is limited to 128 parameters (the model has {self.P}): the tree lives in LDS")
         code, G, index = self._metric(metric, form, index, C)
         if int(max_depth) != max_depth:
@@ -696,10 +721,11 @@ class Plan:
                   temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
         """One draw of multinomial NUTS for every chain under a fixed metric (ey_nuts_step): ``metric``,
         ``form`` and ``index`` as in ``hmc_metric_step``, at most 128 parameters in either form; ``max_depth`` in [1, 10]
-        doublings.  ``v0`` [C, P] replaces the draw of the whitened velocity, ``u`` [C, S] (S >= 21 + 2^max_depth) the
+        doublings.  With EY_NUTS_TREE_DEVICE in ``flags`` and form 'diag' the tree lives in the workspace of
+        ``attach_nuts_tree`` and P is not limited (include/eeyore_amd_nuts_tree.h; the same holds of the run and the warm-up).  ``v0`` [C, P] replaces the draw of the whitened velocity, ``u`` [C, S] (S >= 21 + 2^max_depth) the
         chain's uniform stream in its word layout (1 + 2d the direction of doubling d, 2 + 2d its top-level move, 21 + n
         leaf n).  Returns accepted (the state moved), depth, n_leapfrog, divergent, accept_stat, energy, each [C]."""
-        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out, flags)
         step_vec = self._opt(step_vec, C)
         S = 0
         if u is not None:
@@ -725,7 +751,7 @@ class Plan:
                  depth_rec=None, divergent_rec=None, out=None):
         """``n_iters`` iterations of ``nuts_step`` on the in-kernel streams in one launch (ey_nuts_run), bit for bit;
         records as in ``hmc_run``, and ``depth_rec`` [n_iters, C] int32, ``divergent_rec`` [n_iters, C] uint8."""
-        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out, flags)
         step_vec = self._opt(step_vec, C)
         lead = (L.ptr(theta), L.ptr(target), L.ptr(grad), L.ptr(metric), code, G, L.ptr(index), float(step),
                 L.ptr(step_vec), int(max_depth))
@@ -741,7 +767,7 @@ class Plan:
         every chain's step on the draw's accept_stat, Welford moments of the state it is left in.  The arguments from
         ``da_state`` on are ``hmc_metric_warmup``'s (``rate_rec`` records accept_stat); with none of them it is
         ``nuts_run``, bit for bit."""
-        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out)
+        C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out, flags)
         n_iters, f64 = int(n_iters), torch.float64
         if da_state is not None or steps_rec is not None:
             if step_vec is not None:  # in/out: the caller's own tensor, not a converted copy

@@ -2,11 +2,11 @@ import torch
 
 from .base import ChainBuffer
 from .hmc import HMC
-from .metric import DiagMetric
+from .metric import DenseMetric, DiagMetric
 from eeyore_amd.tuners import HMCDATuner, PerChainDATuner
 from eeyore_amd import _lib as L
 
-NUTS_MAX_P = 128  # ey_nuts_step keeps the tree's vectors in LDS, in either metric form
+NUTS_MAX_P = 128  # ey_nuts_step keeps the tree's vectors in LDS, in either metric form, unless tree='device'
 
 
 class NUTS(HMC):
@@ -17,7 +17,12 @@ class NUTS(HMC):
     edges or inside the new subtree, a leaf's energy error exceeds 1000 (a divergent draw), or ``max_depth`` (at most 10)
     doublings are made; one wave per chain, so trees of different depth cost load balance only.  ``metric=None`` is the
     identity ``DiagMetric``; otherwise as ``HMC`` ('diag', 'dense', a ``DiagMetric`` / ``DenseMetric``, per chain or
-    indexed through ``_set_metric``).  At most 128 parameters in either form.
+    indexed through ``_set_metric``).  At most 128 parameters in either form with ``tree='lds'``, the default.
+
+    ``tree='device'`` keeps the tree's vectors in a workspace in device memory instead (include/eeyore_amd_nuts_tree.h,
+    DESIGN.md 4.27): the same draw for any number of parameters whose evaluation fits LDS, under a diagonal metric only
+    (``metric=None``, 'diag' or a ``DiagMetric``; a dense one raises ``ValueError``).  The workspace, (12 + 2 max_depth)
+    vectors per chain, is attached to the plan a launch is about to run on and grows with the largest call.
 
     ``theta0`` [C, P] or [P]; ``rng='torch'`` draws the velocity and the draw's table of uniforms on the host (the word
     layout of include/eeyore_amd_nuts.h), ``rng='philox'`` uses the in-kernel streams.  ``PerChainDATuner`` / ``HMCDATuner``
@@ -30,15 +35,21 @@ class NUTS(HMC):
 
     def __init__(self, model, theta0=None, dataloader=None, data0=None, counter=None, step=0.1, max_depth=10, metric=None,
                  tuner=None, chain=None, rng=None, seed=0, chain_offset=0, recompute_initial_grad=False, temperature=None,
-                 init_step_mode='intended'):
+                 init_step_mode='intended', tree='lds'):
+        if tree not in ('lds', 'device'):
+            raise ValueError("NUTS: tree must be 'lds' or 'device'")
         if init_step_mode == 'reference':
             raise ValueError("NUTS: init_step_mode='reference' restates the reference's identity-mass heuristic and has no "
                              "metric form; use 'intended'")
         if int(max_depth) != max_depth or not 1 <= max_depth <= L.EY_NUTS_MAX_DEPTH:
             raise ValueError(f"NUTS: max_depth must be an integer in [1, {L.EY_NUTS_MAX_DEPTH}]")
         P = model.num_params()
-        if P > NUTS_MAX_P:
-            raise ValueError(f"NUTS is limited to {NUTS_MAX_P} parameters (the model has {P}): the tree lives in LDS")
+        if tree == 'lds' and P > NUTS_MAX_P:
+            raise ValueError(f"NUTS is limited to {NUTS_MAX_P} parameters (the model has {P}): the tree lives in LDS; "
+                             "pass tree='device' for a diagonal metric")
+        if tree == 'device' and (metric == 'dense' or isinstance(metric, DenseMetric)):
+            raise ValueError("NUTS: tree='device' serves a diagonal metric only (metric=None, 'diag' or a DiagMetric)")
+        self.tree = tree
         if metric is None:
             metric = DiagMetric.identity(P, dtype=model.dtype, device=model.device)
         self.max_depth = int(max_depth)
@@ -50,6 +61,19 @@ class NUTS(HMC):
 
     def leapfrog(self, position0, momentum0, x, y):
         raise ValueError("NUTS.leapfrog: a NUTS trajectory has no fixed length; use HMC.leapfrog")
+
+    def _set_metric(self, metric, index=None):
+        if getattr(self, 'tree', 'lds') == 'device' and isinstance(metric, DenseMetric):
+            raise ValueError("NUTS: tree='device' serves a diagonal metric only")
+        super()._set_metric(metric, index)
+
+    def _flags(self, plan):
+        """The flags of a launch on ``plan``; with tree='device' the plan first gets a workspace for this sampler's tree."""
+        flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
+        if self.tree == 'device':
+            plan.attach_nuts_tree(self.num_chains, self.max_depth)
+            flags |= L.EY_NUTS_TREE_DEVICE
+        return flags
 
     # -- one draw
     def _nuts_randoms(self, C, P):
@@ -72,7 +96,7 @@ class NUTS(HMC):
             self._target, self._grad = plan.log_target_grad(self._theta, temp=temp)
         v0, u = self._nuts_randoms(*self._theta.shape)
         step, step_vec = self._step_args()
-        flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
+        flags = self._flags(plan)
         out = plan.nuts_step(self._theta, self._target, self._grad, step, self.max_depth, self._metric, self._metric_form,
                              index=self._metric_index, v0=v0, u=u, step_vec=step_vec, temp=temp, seed=self.seed,
                              it=self._iter, chain_offset=self.chain_offset, flags=flags)
@@ -121,12 +145,13 @@ class NUTS(HMC):
 
     def _run_block(self, plan, k, rec):
         step, step_vec = self._step_args()
-        flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
+        flags = self._flags(plan)
         return plan.nuts_run(self._theta, self._target, self._grad, step, self.max_depth, self._metric, self._metric_form,
                              k, index=self._metric_index, step_vec=step_vec, temp=self._temp(), seed=self.seed,
                              it=self._iter, chain_offset=self.chain_offset, flags=flags, **rec)
 
     # -- the hook of tuners.WindowedAdaptation.warm_up: the sampler's own warm-up launch (the tuner's num_steps is unused)
     def _warmup_launch(self, plan, num_steps, k, **kw):
+        kw['flags'] = kw.get('flags', 0) | self._flags(plan)
         return plan.nuts_warmup(self._theta, self._target, self._grad, 0.0, self.max_depth, self._metric,
                                 self._metric_form, k, **kw)
