@@ -1871,6 +1871,81 @@ __host__ __device__ static size_t hmc_metric_lds(const EyModel& m, int form, siz
     }                                                                                   \
   } while (0)
 
+// ---- steps the metric kernels share (k_hmc_metric, k_hmc_metric_warmup; k_nuts and k_nuts_ws through ey_nuts_draw.h)
+// The chain's metric into LDS, once per launch: the row of `metric` chosen as EY_CHAIN_INDEX says, a dense factor packed
+// into S, a diagonal's scales copied into sd.  The caller's barrier follows.  DECLARES g.  Reads: T, FORM, metric,
+// metric_index, G, c, P, lane, S, sd.
+#define EY_METRIC_STAGE()                                \
+  EY_CHAIN_INDEX(g, metric_index);                       \
+  if constexpr (FORM == EY_METRIC_TRIL) {                \
+    const T* Lg = metric + g * (int64_t)P * P;           \
+    EY_TRIL_PACK(S, Lg);                                 \
+  } else {                                               \
+    const T* sg = metric + g * (int64_t)P;               \
+    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];  \
+  }
+// kin = |v|^2 over the wave: a lane pass, the idle lanes' inputs selected to zero.  Reads: T, P, lane, v.
+#define EY_KINETIC(kin)                \
+  do {                                 \
+    kin = T(0);                        \
+    EY_LANE_PASS(P, i, on) {           \
+      const T vz = on ? v[i] : T(0);   \
+      kin += vz * vz;                  \
+    }                                  \
+    kin = wave_sum(kin);               \
+  } while (0)
+// The two warm-up epilogues of a draw, as the comment of k_hmc_metric_warmup describes them: the dual-averaging step on
+// `rate` into the step variable `eps` (and step_vec[c]), then the Welford moments of x_i, an expression in i for element i
+// of the state the chain is left in.  Both conditions are wave-uniform.  Reads: T, FORM, P, lane, c, it, w, da, rate,
+// step_vec, mean_c, M2_c, dlt.
+#define EY_WARM_EPILOGUES(x_i, eps)                                                                                  \
+  do {                                                                                                               \
+    if (w.da_state && it < w.da_n) {                                                                                 \
+      eps = (T)ey_da_update(da, w.da_table + 3 * it, (double)rate, w.d, w.has_eub != 0, w.logeub, it == w.final_it); \
+      if (lane == 0) step_vec[c] = eps;                                                                              \
+    }                                                                                                                \
+    if (mean_c) {                                                                                                    \
+      const double ey_cnt_ = (double)(w.count + it + 1);                                                             \
+      const double ey_f_ = (ey_cnt_ - 1.0) / ey_cnt_;                                                                \
+      /* l.gr has been read for the last time: dlt takes its place */                                                \
+      if constexpr (FORM == EY_METRIC_TRIL) __syncthreads();                                                         \
+      EY_LANE_PASS(P, i, on) {                                                                                       \
+        (void)on;                                                                                                    \
+        const double x = (double)(x_i);                                                                              \
+        const double mu = mean_c[i];                                                                                 \
+        const double dx = x - mu;                                                                                    \
+        mean_c[i] = mu + dx / ey_cnt_;                                                                               \
+        if constexpr (FORM == EY_METRIC_TRIL) {                                                                      \
+          dlt[i] = dx;                                                                                               \
+        } else {                                                                                                     \
+          M2_c[i] = M2_c[i] + ey_f_ * (dx * dx);                                                                     \
+        }                                                                                                            \
+      }                                                                                                              \
+      if constexpr (FORM == EY_METRIC_TRIL) {                                                                        \
+        __syncthreads();                                                                                             \
+        for (int i = 0; i < P; ++i) {                                                                                \
+          const double fi = ey_f_ * dlt[i];                                                                          \
+          double* row = M2_c + (int64_t)i * P;                                                                       \
+          _Pragma("unroll")                                                                                          \
+          for (int r = 0; r < 2; ++r) {                                                                              \
+            if (r * WAVE > i) break; /* a round wholly beyond the diagonal: wave-uniform */                          \
+            const int j = lane + r * WAVE;                                                                           \
+            const int jj = j <= i ? j : i;                                                                           \
+            row[jj] = row[jj] + fi * dlt[jj];                                                                        \
+          }                                                                                                          \
+        }                                                                                                            \
+      }                                                                                                              \
+    }                                                                                                                \
+  } while (0)
+
+// The LDS limit of the diagonal form, which holds no triangle: the refusal under the sampler's name.
+static int diag_limit(const std::string& name, size_t bytes) {
+  if (bytes > 160 * 1024)
+    EY_FAIL(EY_ERR_UNSUPPORTED, name + " with a diagonal metric: the model's evaluation image and the scales (" +
+                                    std::to_string(bytes) + " bytes) do not fit the 160 KiB LDS of a CU");
+  return EY_OK;
+}
+
 #if EY_GEN_PART == 0  // (to the end of the file)
 template <typename T, class TINY, int FORM>
 __global__ void __launch_bounds__(WAVE) k_hmc_metric(EyModel m, T* theta, T* target, T* grad, const T* metric, int64_t G,
@@ -1890,14 +1965,7 @@ __global__ void __launch_bounds__(WAVE) k_hmc_metric(EyModel m, T* theta, T* tar
   const bool ht = temp != nullptr;
   const T tc = ht ? temp[c] : T(1);
   const T eps = step_vec ? step_vec[c] : step;
-  EY_CHAIN_INDEX(g, metric_index);
-  if constexpr (FORM == EY_METRIC_TRIL) {
-    const T* Lg = metric + g * (int64_t)P * P;
-    EY_TRIL_PACK(S, Lg);
-  } else {
-    const T* sg = metric + g * (int64_t)P;
-    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];
-  }
+  EY_METRIC_STAGE();
   (void)S; (void)sd; (void)R;
   __syncthreads();
   T t_state = target[c];
@@ -1921,12 +1989,7 @@ __global__ void __launch_bounds__(WAVE) k_hmc_metric(EyModel m, T* theta, T* tar
     T t = t_state;
     if (recompute) t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
     EY_LEAPFROG_METRIC(t);
-    kin = T(0);
-    EY_LANE_PASS(P, i, on) {
-      const T vz = on ? v[i] : T(0);
-      kin += vz * vz;
-    }
-    kin = wave_sum(kin);
+    EY_KINETIC(kin);
     const T h_prop = -t + T(0.5) * kin;
     T rate = Num<T>::exp(h_cur - h_prop);
     if (rate > T(1)) rate = T(1);
@@ -1974,12 +2037,9 @@ int ey_generic_hmc_metric(ey_plan* pl, void* theta, void* target, void* grad, co
                           const void* metric_index, const void* v0, const void* u, double step, const void* step_vec, int L,
                           const EyDraw& d, void* rate, void* hcur, void* hprop) {
   const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
-  if (form == EY_METRIC_TRIL) {
-    if (int rc = tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)) return rc;
-  } else if (bytes > 160 * 1024) {
-    EY_FAIL(EY_ERR_UNSUPPORTED, "HMC with a diagonal metric: the model's evaluation image and the scales (" +
-                                    std::to_string(bytes) + " bytes) do not fit the 160 KiB LDS of a CU");
-  }
+  if (int rc = form == EY_METRIC_TRIL ? tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)
+                                      : diag_limit("HMC", bytes))
+    return rc;
   EyDraw dr = d;
   dr.log_rate = rate;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc_metric, pl, theta, target, grad, metric, form, G, metric_index, v0, u,
@@ -2019,14 +2079,7 @@ __global__ void __launch_bounds__(WAVE) k_hmc_metric_warmup(EyModel m, T* theta,
   const bool ht = temp != nullptr;
   const T tc = ht ? temp[c] : T(1);
   T eps = step_vec ? step_vec[c] : step;
-  EY_CHAIN_INDEX(g, metric_index);
-  if constexpr (FORM == EY_METRIC_TRIL) {
-    const T* Lg = metric + g * (int64_t)P * P;
-    EY_TRIL_PACK(S, Lg);
-  } else {
-    const T* sg = metric + g * (int64_t)P;
-    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];
-  }
+  EY_METRIC_STAGE();
   (void)S; (void)sd; (void)R; (void)dlt;
   double da[3] = {0.0, 0.0, 0.0};
   if (w.da_state) {
@@ -2055,12 +2108,7 @@ __global__ void __launch_bounds__(WAVE) k_hmc_metric_warmup(EyModel m, T* theta,
     T t = t_state;
     if (recompute) t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
     EY_LEAPFROG_METRIC(t);
-    kin = T(0);
-    EY_LANE_PASS(P, i, on) {
-      const T vz = on ? v[i] : T(0);
-      kin += vz * vz;
-    }
-    kin = wave_sum(kin);
+    EY_KINETIC(kin);
     const T h_prop = -t + T(0.5) * kin;
     T rate = Num<T>::exp(h_cur - h_prop);
     if (rate > T(1)) rate = T(1);
@@ -2080,41 +2128,7 @@ __global__ void __launch_bounds__(WAVE) k_hmc_metric_warmup(EyModel m, T* theta,
       if (w.steps_rec) static_cast<T*>(w.steps_rec)[(int64_t)it * C + c] = eps;
       if (w.rate_rec) static_cast<T*>(w.rate_rec)[(int64_t)it * C + c] = rate;
     }
-    if (w.da_state && it < w.da_n) {  // wave-uniform
-      eps = (T)ey_da_update(da, w.da_table + 3 * it, (double)rate, w.d, w.has_eub != 0, w.logeub, it == w.final_it);
-      if (lane == 0) step_vec[c] = eps;
-    }
-    if (mean_c) {  // wave-uniform
-      const double n = (double)(w.count + it + 1);
-      const double f = (n - 1.0) / n;
-      if constexpr (FORM == EY_METRIC_TRIL) __syncthreads();  // l.gr has been read for the last time: dlt takes its place
-      EY_LANE_PASS(P, i, on) {
-        (void)on;
-        const double x = (double)(acc_ ? l.th[i] : theta[c * P + i]);
-        const double mu = mean_c[i];
-        const double dx = x - mu;
-        mean_c[i] = mu + dx / n;
-        if constexpr (FORM == EY_METRIC_TRIL) {
-          dlt[i] = dx;
-        } else {
-          M2_c[i] = M2_c[i] + f * (dx * dx);
-        }
-      }
-      if constexpr (FORM == EY_METRIC_TRIL) {
-        __syncthreads();
-        for (int i = 0; i < P; ++i) {
-          const double fi = f * dlt[i];
-          double* row = M2_c + (int64_t)i * P;
-          _Pragma("unroll")
-          for (int r = 0; r < 2; ++r) {
-            if (r * WAVE > i) break;  // a round wholly beyond the diagonal: wave-uniform
-            const int j = lane + r * WAVE;
-            const int jj = j <= i ? j : i;
-            row[jj] = row[jj] + fi * dlt[jj];
-          }
-        }
-      }
-    }
+    EY_WARM_EPILOGUES(acc_ ? l.th[i] : theta[c * P + i], eps);
     __syncthreads();
   }
   if (w.da_state && lane == 0) {
@@ -2142,12 +2156,9 @@ int ey_generic_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* g
                                  int64_t G, const void* metric_index, double step, void* step_vec, int L, const EyDraw& d,
                                  const EyWarm& w) {
   const size_t bytes = ey_generic_hmc_metric_lds(pl, form);
-  if (form == EY_METRIC_TRIL) {
-    if (int rc = tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)) return rc;
-  } else if (bytes > 160 * 1024) {
-    EY_FAIL(EY_ERR_UNSUPPORTED, "HMC with a diagonal metric: the model's evaluation image and the scales (" +
-                                    std::to_string(bytes) + " bytes) do not fit the 160 KiB LDS of a CU");
-  }
+  if (int rc = form == EY_METRIC_TRIL ? tril_limits(pl, "HMC with a dense metric", "the factor", "the factor", bytes)
+                                      : diag_limit("HMC", bytes))
+    return rc;
   EyDraw dr = d;
   dr.log_rate = nullptr;
   return EY_TINY_DISPATCH(tiny_dispatch, launch_hmc_metric_warmup, pl, theta, target, grad, metric, form, G, metric_index,

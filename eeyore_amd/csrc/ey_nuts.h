@@ -31,3 +31,18 @@ int64_t ey_nuts_ws_bytes(const ey_plan* pl, int64_t C, int max_depth);
 int ey_nuts_ws_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int64_t G,
                       const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
                       const EyWarm& w);
+
+// The launch of one wave per chain.  The LDS limit of an instantiation is raised once per plan, to the whole 160 KiB
+// (DESIGN.md 4.9.1): the limit belongs to the kernel, not to a launch, and `attr` is the plan's slot for the kernel that has
+// it (ey_plan::nuts_attr, ey_plan::nuts_ws_attr).
+template <typename... Ps, typename... As>
+static int launch_nuts_kernel(const void** attr, void (*kernel)(Ps...), int64_t C, size_t bytes, hipStream_t s, As... args) {
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (bytes > 48 * 1024 && *attr != fn) {
+    EY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    *attr = fn;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)C), dim3(64), bytes, s, args...);
+  EY_HIP(hipGetLastError());
+  return EY_OK;
+}

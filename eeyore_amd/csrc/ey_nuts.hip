@@ -5,309 +5,26 @@
 #define EY_GEN_PART 1
 #include "ey_generic.hip"
 
-#include <limits>
-
 #include "ey_nuts.h"
 
-// One wave per chain, as k_hmc_metric: the evaluation image (th, gr, a = v [, the diagonal scales]) and the packed factor
-// where there is one, then NUTS_NVEC vectors of Ppad elements:
-//   the two edges of the tree (theta, v, g each), the tree's proposal and the new subtree's candidate (theta, g each: the
-//   gradient is kept with a candidate, nothing is re-evaluated when the draw ends), rho of the tree and of the new subtree,
-//   and EY_NUTS_MAX_DEPTH checkpoints (v, rho' up to and including the checkpoint's leaf) for the sub-block checks.
-// Multinomial NUTS, iterative: a subtree of 2^d leaves is one loop over its leaves; the aligned blocks that end at leaf k are
-// checked from checkpoints, one per trailing 1-bit of k (an even k stores slot popcount(k >> 1), an odd k reads slots from
-// popcount(k >> 1) downward).  Every decision is wave-uniform (the sums are butterfly all-reduces, the uniforms are read by
-// every lane) and is moved to a scalar register before it is branched on, so the loops below run under a full EXEC mask.
+// The tree lives in LDS behind k_hmc_metric's image (and the packed factor where there is one): NUTS_NVEC vectors of P
+// rounded up to 4 elements, in the order ey_nuts_draw.h lists.
 #define NUTS_NVEC (12 + 2 * EY_NUTS_MAX_DEPTH)
 
 __host__ __device__ static size_t nuts_lds(const EyModel& m, int form, size_t esz) {
   return hmc_metric_lds(m, form, esz) + esz * (size_t)NUTS_NVEC * ((m.P + 3) & ~3);
 }
 
-// log(exp(a) + exp(b)), branch for branch as numpy's logaddexp (a = b covers two infinities of one sign)
-template <typename T>
-__device__ __forceinline__ T nuts_logaddexp(T a, T b) {
-  if (a == b) return a + T(0.693147180559945309417232121458176568);
-  const T d = a - b;
-  if (d > T(0)) return a + Num<T>::log1p(Num<T>::exp(-d));
-  if (d <= T(0)) return b + Num<T>::log1p(Num<T>::exp(d));
-  return d;  // NaN
-}
-
-// a wave-uniform decision as a scalar
-#define NUTS_UNIFORM(cond) (__builtin_amdgcn_readfirstlane((cond) ? 1 : 0) != 0)
-// the uniform at block word `word` of the draw: the caller's table, or the chain's stream.  Reads: T, u_in, S_u, c, ru.
-#define NUTS_U(word) (u_in ? u_in[c * S_u + (int64_t)(word)] : ey_rng_uniform_at<T>(ru, (uint32_t)(word)))
-// a . rho > 0 and b . rho > 0, `rho_i` an expression in i: the U-turn criterion between two ends in the whitened velocity.
-// DECLARES `ok`.  Reads: T, P, lane.
-#define NUTS_CRITERION(ok, a, b, rho_i)                 \
-  bool ok;                                              \
-  do {                                                  \
-    T ey_sa_ = T(0), ey_sb_ = T(0);                     \
-    EY_LANE_PASS(P, i, on) {                            \
-      const T ey_r_ = (rho_i);                          \
-      const T ey_rz_ = on ? ey_r_ : T(0);               \
-      ey_sa_ += (a)[i] * ey_rz_;                        \
-      ey_sb_ += (b)[i] * ey_rz_;                        \
-    }                                                   \
-    ey_sa_ = wave_sum(ey_sa_);                          \
-    ey_sb_ = wave_sum(ey_sb_);                          \
-    ok = NUTS_UNIFORM(ey_sa_ > T(0) && ey_sb_ > T(0));  \
-  } while (0)
-
-template <typename T, class TINY, int FORM>
-__global__ void __launch_bounds__(WAVE) k_nuts(EyModel m, T* theta, T* target, T* grad, const T* metric, int64_t G,
-                                               const int* metric_index, const T* v0, const T* u_in, int64_t S_u, T step,
-                                               T* step_vec, int max_depth, int recompute, EyNuts nu, EyWarm w,
-                                               const T* temp, uint64_t seed, uint64_t iter0, uint64_t chain_offset,
-                                               unsigned char* accepted, T* rate_o, EyRun run, int64_t C) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const Lds<T> l = carve<T>(m, smem, FORM == EY_METRIC_TRIL ? 3 : 4);
-  const int P = m.P;
-  const int Ppad = (P + 3) & ~3;
-  T* S = reinterpret_cast<T*>(smem + lds_bytes(m, 3, sizeof(T)));  // EY_METRIC_TRIL: the packed factor
-  T* sd = l.b;                                                     // EY_METRIC_DIAG: the scales
-  T* v = l.a;
-  double* dlt = reinterpret_cast<double*>(l.gr);                   // EY_METRIC_TRIL moments: x - mean_old, between draws
-  T* nv = reinterpret_cast<T*>(smem + hmc_metric_lds(m, FORM, sizeof(T)));
-  T* e_left = nv;               // an edge: theta, then v at + Ppad, g at + 2 Ppad
-  T* e_right = nv + 3 * Ppad;
-  T* p_th = nv + 6 * Ppad;   // the tree's proposal
-  T* p_g = nv + 7 * Ppad;
-  T* c_th = nv + 8 * Ppad;   // the new subtree's candidate
-  T* c_g = nv + 9 * Ppad;
-  T* rho = nv + 10 * Ppad;
-  T* rhop = nv + 11 * Ppad;
-  T* ck = nv + 12 * Ppad;    // checkpoint s: v at ck + 2 s Ppad, rho' at ck + (2 s + 1) Ppad
-  const int R = P > WAVE ? 2 : 1;  // the rows (and columns) of a lane: wave-uniform
-  const int64_t c = blockIdx.x;
-  const int lane = threadIdx.x;
-  const bool ht = temp != nullptr;
-  const T tc = ht ? temp[c] : T(1);
-  T eps0 = step_vec ? step_vec[c] : step;
-  EY_CHAIN_INDEX(g, metric_index);
-  if constexpr (FORM == EY_METRIC_TRIL) {
-    const T* Lg = metric + g * (int64_t)P * P;
-    EY_TRIL_PACK(S, Lg);
-  } else {
-    const T* sg = metric + g * (int64_t)P;
-    for (int i = lane; i < P; i += WAVE) sd[i] = sg[i];
-  }
-  (void)S; (void)sd; (void)R; (void)dlt;
-  double da[3] = {0.0, 0.0, 0.0};
-  if (w.da_state) {
-    for (int k = 0; k < 3; ++k) da[k] = w.da_state[3 * c + k];
-  }
-  double* mean_c = w.mean ? w.mean + c * (int64_t)P : nullptr;
-  double* M2_c = w.M2 ? w.M2 + c * (FORM == EY_METRIC_TRIL ? (int64_t)P * P : (int64_t)P) : nullptr;
-  const T ninf = -std::numeric_limits<T>::infinity();
-  __syncthreads();
-  T t_state = target[c];
-  for (int it = 0; it < run.n_iters; ++it) {
-    const uint64_t iter = iter0 + (uint64_t)it;
-    // v ~ N(0, I): k_hmc_metric's draw
-    const EyRng rn = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_NORMAL);
-    const EyRng ru = ey_rng_make(seed, chain_offset + (uint64_t)c, iter, EY_STREAM_UNIFORM);
-    T kin = T(0);
-    if (!v0) fill_normals<T>(v, rn, P);
-    EY_LANE_PASS(P, i, on) {
-      l.th[i] = theta[c * P + i];
-      l.gr[i] = grad[c * P + i];
-      const T vi = v0 ? v0[c * P + i] : v[i];
-      v[i] = vi;
-      const T vz = on ? vi : T(0);
-      kin += vz * vz;
-    }
-    kin = wave_sum(kin);
-    const T H0 = -t_state + T(0.5) * kin;
-    __syncthreads();
-    if (recompute) (void)eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
-    // the tree is the single leaf (theta, v, g): both edges, the proposal, rho
-    for (int i = lane; i < P; i += WAVE) {
-      const T thi = l.th[i], vi = v[i], gi = l.gr[i];
-      e_left[i] = thi; e_right[i] = thi; p_th[i] = thi;
-      e_left[Ppad + i] = vi; e_right[Ppad + i] = vi; rho[i] = vi;
-      e_left[2 * Ppad + i] = gi; e_right[2 * Ppad + i] = gi; p_g[i] = gi;
-    }
-    T t_prop = t_state, H_prop = H0, W = T(0), acc_sum = T(0);
-    int depth = 0, n = 0;
-    bool divergent = false, moved = false;
-    while (depth < max_depth) {
-      // 1. the direction; the edge it extends becomes the integrator's state.  Backward integrates with -eps: velocities
-      //    keep their forward-time sign, nothing is negated
-      const bool fwd = NUTS_UNIFORM(!(NUTS_U(1 + 2 * depth) < T(0.5)));
-      const T eps = fwd ? eps0 : -eps0;
-      T* edge = fwd ? e_right : e_left;
-      __syncthreads();
-      for (int i = lane; i < P; i += WAVE) {
-        l.th[i] = edge[i];
-        v[i] = edge[Ppad + i];
-        l.gr[i] = edge[2 * Ppad + i];
-        rhop[i] = T(0);
-      }
-      __syncthreads();
-      // 2. the new subtree: 2^depth leaves, one leapfrog step each
-      T Wp = ninf, t_cand = T(0), H_cand = T(0);
-      bool valid = true;
-      const int n_leaf = 1 << depth;
-      for (int k = 0; k < n_leaf; ++k) {
-        EY_METRIC_KICK(T(0.5) * eps);
-        EY_METRIC_DRIFT();
-        const T t = eval_target<T, true, TINY>(m, l, l.th, l.gr, ht, tc, nullptr, nullptr);
-        EY_METRIC_KICK(T(0.5) * eps);
-        kin = T(0);
-        EY_LANE_PASS(P, i, on) {
-          const T vz = on ? v[i] : T(0);
-          kin += vz * vz;
-        }
-        kin = wave_sum(kin);
-        const T H = -t + T(0.5) * kin;
-        T delta = H0 - H;
-        if (!(delta == delta)) delta = ninf;
-        if (NUTS_UNIFORM(-delta > T(1000))) {  // a divergent draw
-          divergent = true;
-          valid = false;
-          break;
-        }
-        Wp = nuts_logaddexp(Wp, delta);
-        // reservoir sampling of the subtree's candidate: the first leaf is always taken
-        if (NUTS_UNIFORM(NUTS_U(1 + 2 * EY_NUTS_MAX_DEPTH + n) < Num<T>::exp(delta - Wp))) {
-          for (int i = lane; i < P; i += WAVE) {
-            c_th[i] = l.th[i];
-            c_g[i] = l.gr[i];
-          }
-          t_cand = t;
-          H_cand = H;
-        }
-        for (int i = lane; i < P; i += WAVE) rhop[i] = rhop[i] + v[i];
-        const T a1 = Num<T>::exp(delta);
-        acc_sum += a1 < T(1) ? a1 : T(1);
-        n += 1;
-        // the aligned blocks of 2^j leaves that end at k, from the checkpoints
-        if ((k & 1) == 0) {
-          T* cv = ck + 2 * __popc((unsigned)(k >> 1)) * Ppad;
-          for (int i = lane; i < P; i += WAVE) {
-            cv[i] = v[i];
-            cv[Ppad + i] = rhop[i];
-          }
-          __syncthreads();
-        } else {
-          __syncthreads();
-          int slot = __popc((unsigned)(k >> 1));
-          for (int kk = k; kk & 1; kk >>= 1, --slot) {
-            const T* cv = ck + 2 * slot * Ppad;
-            NUTS_CRITERION(ok, cv, v, rhop[i] - cv[Ppad + i] + cv[i]);
-            if (!ok) {
-              valid = false;
-              break;
-            }
-          }
-          if (!valid) break;
-        }
-      }
-      // 3. an invalid subtree is discarded and the draw stops
-      if (!valid) break;
-      // 4. biased progressive sampling of the tree's proposal; the edge moves; the criterion between the tree's edges
-      if (NUTS_UNIFORM(NUTS_U(2 + 2 * depth) < Num<T>::exp(Wp - W))) {
-        for (int i = lane; i < P; i += WAVE) {
-          p_th[i] = c_th[i];
-          p_g[i] = c_g[i];
-        }
-        t_prop = t_cand;
-        H_prop = H_cand;
-        moved = true;
-      }
-      W = nuts_logaddexp(W, Wp);
-      for (int i = lane; i < P; i += WAVE) {
-        rho[i] = rho[i] + rhop[i];
-        edge[i] = l.th[i];
-        edge[Ppad + i] = v[i];
-        edge[2 * Ppad + i] = l.gr[i];
-      }
-      depth += 1;
-      __syncthreads();
-      NUTS_CRITERION(go, e_left + Ppad, e_right + Ppad, rho[i]);
-      if (!go) break;
-    }
-    // the state becomes the proposal
-    if (moved) {
-      t_state = t_prop;
-      for (int i = lane; i < P; i += WAVE) {
-        theta[c * P + i] = p_th[i];
-        grad[c * P + i] = p_g[i];
-      }
-    }
-    const T rate = n > 0 ? acc_sum / (T)n : T(0);
-    EY_RECORD_SAMPLE(true, i, p_th[i]);
-    record_draw<T>(lane == 0, c, it, C, moved, t_prop, t_state, rate, target, accepted, rate_o, run);
-    if (lane == 0) {
-      if (nu.depth) nu.depth[c] = depth;
-      if (nu.n_leapfrog) nu.n_leapfrog[c] = n;
-      if (nu.divergent) nu.divergent[c] = divergent ? 1 : 0;
-      if (nu.energy) static_cast<T*>(nu.energy)[c] = H_prop;
-      if (nu.depth_rec) nu.depth_rec[(int64_t)it * C + c] = depth;
-      if (nu.div_rec) nu.div_rec[(int64_t)it * C + c] = divergent ? 1 : 0;
-      if (w.steps_rec) static_cast<T*>(w.steps_rec)[(int64_t)it * C + c] = eps0;
-      if (w.rate_rec) static_cast<T*>(w.rate_rec)[(int64_t)it * C + c] = rate;
-    }
-    // the two epilogues of k_hmc_metric_warmup, copied (sharing them would have meant rewriting that kernel's text), on
-    // rate := the draw's mean accept statistic and x := the state the chain is left in, which is the proposal
-    if (w.da_state && it < w.da_n) {  // wave-uniform
-      eps0 = (T)ey_da_update(da, w.da_table + 3 * it, (double)rate, w.d, w.has_eub != 0, w.logeub, it == w.final_it);
-      if (lane == 0) step_vec[c] = eps0;
-    }
-    if (mean_c) {  // wave-uniform
-      const double cnt = (double)(w.count + it + 1);
-      const double f = (cnt - 1.0) / cnt;
-      if constexpr (FORM == EY_METRIC_TRIL) __syncthreads();  // l.gr has been read for the last time: dlt takes its place
-      EY_LANE_PASS(P, i, on) {
-        (void)on;
-        const double x = (double)p_th[i];
-        const double mu = mean_c[i];
-        const double dx = x - mu;
-        mean_c[i] = mu + dx / cnt;
-        if constexpr (FORM == EY_METRIC_TRIL) {
-          dlt[i] = dx;
-        } else {
-          M2_c[i] = M2_c[i] + f * (dx * dx);
-        }
-      }
-      if constexpr (FORM == EY_METRIC_TRIL) {
-        __syncthreads();
-        for (int i = 0; i < P; ++i) {
-          const double fi = f * dlt[i];
-          double* row = M2_c + (int64_t)i * P;
-          _Pragma("unroll")
-          for (int r = 0; r < 2; ++r) {
-            if (r * WAVE > i) break;  // a round wholly beyond the diagonal: wave-uniform
-            const int j = lane + r * WAVE;
-            const int jj = j <= i ? j : i;
-            row[jj] = row[jj] + fi * dlt[jj];
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (w.da_state && lane == 0) {
-    w.da_state[3 * c] = da[0];
-    w.da_state[3 * c + 1] = da[1];
-  }
-}
-
-// the LDS limit of an instantiation is raised once per plan, to the whole 160 KiB: the limit belongs to
-// the kernel, not to a launch
-template <typename... Ps, typename... As>
-static int launch_nuts_kernel(ey_plan* pl, void (*kernel)(Ps...), int64_t C, size_t bytes, hipStream_t s, As... args) {
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  if (bytes > 48 * 1024 && pl->nuts_attr != fn) {
-    EY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    pl->nuts_attr = fn;
-  }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)C), dim3(WAVE), bytes, s, args...);
-  EY_HIP(hipGetLastError());
-  return EY_OK;
-}
+// the draw itself: ey_nuts_draw.h writes the body of the kernel named here
+#define NUTS_TREE_IN_WS 0
+#define NUTS_KERNEL_HEAD                                                                                             \
+  template <typename T, class TINY, int FORM>                                                                        \
+  __global__ void __launch_bounds__(WAVE) k_nuts(EyModel m, T* theta, T* target, T* grad, const T* metric, int64_t G, \
+                                                 const int* metric_index, const T* v0, const T* u_in, int64_t S_u, T step, \
+                                                 T* step_vec, int max_depth, int recompute, EyNuts nu, EyWarm w,     \
+                                                 const T* temp, uint64_t seed, uint64_t iter0, uint64_t chain_offset, \
+                                                 unsigned char* accepted, T* rate_o, EyRun run, int64_t C)
+#include "ey_nuts_draw.h"
 
 template <typename T, class TINY>
 static int launch_nuts(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
@@ -316,12 +33,14 @@ static int launch_nuts(ey_plan* pl, void* theta, void* target, void* grad, const
   const size_t bytes = ey_nuts_lds(pl, form);
   const int recompute = (d.flags & EY_RECOMPUTE_INITIAL_GRAD) != 0;
   if (form == EY_METRIC_TRIL)
-    return launch_nuts_kernel(pl, k_nuts<T, TINY, EY_METRIC_TRIL>, d.C, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
-                              (const T*)metric, G, (const int*)metric_index, (const T*)nu.v0, (const T*)nu.u, nu.S, (T)step,
-                              (T*)step_vec, nu.max_depth, recompute, nu, w, EY_DRAW_ARGS(T, d));
-  return launch_nuts_kernel(pl, k_nuts<T, TINY, EY_METRIC_DIAG>, d.C, bytes, d.s, pl->m, (T*)theta, (T*)target, (T*)grad,
-                            (const T*)metric, G, (const int*)metric_index, (const T*)nu.v0, (const T*)nu.u, nu.S, (T)step,
-                            (T*)step_vec, nu.max_depth, recompute, nu, w, EY_DRAW_ARGS(T, d));
+    return launch_nuts_kernel(&pl->nuts_attr, k_nuts<T, TINY, EY_METRIC_TRIL>, d.C, bytes, d.s, pl->m, (T*)theta,
+                              (T*)target, (T*)grad, (const T*)metric, G, (const int*)metric_index, (const T*)nu.v0,
+                              (const T*)nu.u, nu.S, (T)step, (T*)step_vec, nu.max_depth, recompute, nu, w,
+                              EY_DRAW_ARGS(T, d));
+  return launch_nuts_kernel(&pl->nuts_attr, k_nuts<T, TINY, EY_METRIC_DIAG>, d.C, bytes, d.s, pl->m, (T*)theta,
+                            (T*)target, (T*)grad, (const T*)metric, G, (const int*)metric_index, (const T*)nu.v0,
+                            (const T*)nu.u, nu.S, (T)step, (T*)step_vec, nu.max_depth, recompute, nu, w,
+                            EY_DRAW_ARGS(T, d));
 }
 
 size_t ey_nuts_lds(const ey_plan* pl, int form) { return nuts_lds(pl->m, form, pl->dtype == EY_F32 ? 4 : 8); }

@@ -81,26 +81,57 @@ def test_parity_with_given_randoms(name):
 
 
 # ------------------------------------------------------------------------------------------------ 2. k_nuts's bits
+MVN64 = "mvn64/diag"   # P = 64 = Ppad in both kernels: no lane owns padding, the criterion runs exactly one full round
+
+
+@functools.lru_cache(maxsize=None)
+def _mvn64(dtype):
+    """The plan and the device arguments (as G._device) of one normal target at P = 64, by the recipe of
+    tests/nuts_cases.py: 4 chains whose steps are 0.02, 0.3, 0.9 and 100 times the stability limit under the metric."""
+    from eeyore_amd.plan import Plan
+    P, C = 64, 4
+    rng = np.random.default_rng([P, 17])
+    A = rng.standard_normal((P, P)) / np.sqrt(P)
+    cov = A @ A.T + 0.5 * np.eye(P)
+    tgt = iv.Target([1.0], rng.standard_normal((1, P)), ((cov + cov.T) / 2)[None])
+    s = 0.5 + rng.random(P)
+    M = s[:, None] * tgt.prec[0] * s[None, :]
+    limit = 2.0 / np.sqrt(np.linalg.eigvalsh((M + M.T) / 2).max())
+    pl = Plan.mixture(tgt.c, tgt.mean, tgt.prec, dtype, DEV)
+    assert pl.P == P
+    return pl, dict(th=_t(iv.exact_draws(tgt, C, rng), dtype), steps=_t(limit * np.array([0.02, 0.3, 0.9, 100.0]), dtype),
+                    M=_t(s, dtype), kind="diag", temp=None)
+
+
 @pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
-@pytest.mark.parametrize("name", ["mvn70/diag", "mvn128/diag", "xor/diag"])
+@pytest.mark.parametrize("name", ["mvn70/diag", "mvn128/diag", "xor/diag", MVN64])
 def test_small_p_gives_the_bits_of_the_tree_in_lds(name, dtype):
-    """K = 6 draws of nuts_run on the in-kernel streams with the flag and without: every output, record and the state."""
-    pl, dev = G._plan(name, dtype), G._device(name, dtype)
+    """K draws of nuts_run on the in-kernel streams with the flag and without: every output, record and the state.  K = 6
+    draws of the 11 chains of a case of tests/nuts_cases.py at its max_depth 5; at P = 64, 3 draws of 4 chains at max_depth
+    3, where the first chain's 7 leaves of a fiftieth of the stability limit never turn: every sub-block check runs."""
+    if name == MVN64:
+        (pl, dev), C, max_depth, K = _mvn64(dtype), 4, 3, 3
+    else:
+        pl, dev, C, max_depth, K = G._plan(name, dtype), G._device(name, dtype), nc.C, nc.MAX_DEPTH, K_RUN
     P = pl.P
     a = G._start(pl, dev)
     b = tuple(t.clone() for t in a)
-    ra, rb = G._run_records(nc.C, P, dtype, K_RUN), G._run_records(nc.C, P, dtype, K_RUN)
+    ra, rb = G._run_records(C, P, dtype, K), G._run_records(C, P, dtype, K)
     kw = dict(step_vec=dev["steps"], temp=dev["temp"], seed=SEED, it=IT0)
-    oa = pl.nuts_run(*a, 0.0, nc.MAX_DEPTH, dev["M"], "diag", K_RUN, **kw, **ra)
-    pl.attach_nuts_tree(nc.C, nc.MAX_DEPTH)
+    oa = pl.nuts_run(*a, 0.0, max_depth, dev["M"], "diag", K, **kw, **ra)
+    pl.attach_nuts_tree(C, max_depth)
     try:
-        ob = pl.nuts_run(*b, 0.0, nc.MAX_DEPTH, dev["M"], "diag", K_RUN, flags=FLAG, **kw, **rb)
+        ob = pl.nuts_run(*b, 0.0, max_depth, dev["M"], "diag", K, flags=FLAG, **kw, **rb)
         torch.cuda.synchronize()
     finally:
         pl.detach_nuts_tree()
     _bits_equal(list(a) + [ra[k] for k in ra] + [oa[k] for k in oa], list(b) + [rb[k] for k in ra] + [ob[k] for k in oa])
-    depths = np.bincount(ra["depth_rec"].cpu().numpy().ravel(), minlength=nc.MAX_DEPTH + 1)
-    assert int(ra["accepted_rec"].sum()) > 0 and (depths > 0).sum() >= 4, depths
+    depths = np.bincount(ra["depth_rec"].cpu().numpy().ravel(), minlength=max_depth + 1)
+    assert int(ra["accepted_rec"].sum()) > 0, depths
+    if name == MVN64:
+        assert depths[max_depth] >= K and depths[0] >= K, depths   # the first chain never turns, the last diverges at once
+    else:
+        assert (depths > 0).sum() >= 4, depths
 
 
 # ------------------------------------------------------------------------------------------------ 3. run against step
