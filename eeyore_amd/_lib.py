@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
 include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h, include/eeyore_amd_eslice_fused.h,
-include/eeyore_amd_nuts_tree.h).
+include/eeyore_amd_nuts_tree.h, include/eeyore_amd_nuts_fused.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -152,6 +152,14 @@ NUTS_TREE_SYMBOLS = {
     "ey_plan_attach_nuts_tree": (_i, [_vp, _vp, _i64]),
 }
 
+# ... and what include/eeyore_amd_nuts_fused.h declares, an eighth table: NUTS on the matrix cores for the plans of the mfma32
+# family.  EY_NUTS_FUSED is a bit of the flags of the three NUTS entry points (it implies EY_NUTS_TREE_DEVICE);
+# ey_nuts_kernel says which kernel serves a plan under given flags, b"mfma32" or b"generic".
+EY_NUTS_FUSED = 16
+NUTS_FUSED_SYMBOLS = {
+    "ey_nuts_kernel": (ct.c_char_p, [_vp, _u32]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -184,7 +192,8 @@ def lib():
         L = ct.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
                                   + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())
-                                  + list(ESLICE_FUSED_SYMBOLS.items()) + list(NUTS_TREE_SYMBOLS.items())):
+                                  + list(ESLICE_FUSED_SYMBOLS.items()) + list(NUTS_TREE_SYMBOLS.items())
+                                  + list(NUTS_FUSED_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -1009,7 +1009,13 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
   if (!mean != !M2) return f.refuse("mean and M2 go together: exactly one of them is null");
   if (mean && count < 0) return f.refuse("count must be >= 0");
   // the tree in device memory (include/eeyore_amd_nuts_tree.h): an undersized workspace would be stores out of bounds
-  const bool tree_ws = (d.flags & EY_NUTS_TREE_DEVICE) != 0;
+  // EY_NUTS_FUSED (include/eeyore_amd_nuts_fused.h): the same workspace, the draw on k_nuts_mfma
+  const bool fused = (d.flags & EY_NUTS_FUSED) != 0;
+  if (fused) {
+    if (form != EY_METRIC_DIAG) return f.refuse("EY_NUTS_FUSED serves the diagonal metric only (form EY_METRIC_DIAG)");
+    if (d.flags & EY_FORCE_GENERIC) return f.refuse("EY_NUTS_FUSED and EY_FORCE_GENERIC contradict each other");
+  }
+  const bool tree_ws = fused || (d.flags & EY_NUTS_TREE_DEVICE) != 0;
   if (tree_ws) {
     if (form != EY_METRIC_DIAG)
       return f.refuse("EY_NUTS_TREE_DEVICE serves the diagonal metric only (form EY_METRIC_DIAG)");
@@ -1020,6 +1026,9 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
       return f.refuse(("the attached workspace of " + std::to_string(pl->nuts_tree_bytes) + " bytes is smaller than the " +
                        std::to_string(need) + " bytes the tree of this call needs (ey_nuts_tree_bytes)").c_str());
   }
+  if (fused && !use_mfma32(pl))
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": EY_NUTS_FUSED serves the plans of the mfma32 family with the batch "
+                                "they hold; this plan's kernel (ey_plan_kernel) is \"" + ey_plan_kernel(pl) + "\"");
   EY_TRY(f.ready(true));
   EyWarm w;
   w.da_state = (double*)da_state;
@@ -1034,6 +1043,8 @@ static int nuts_impl(ey_plan* pl, void* theta, void* target, void* grad, const v
   w.count = count;
   w.steps_rec = steps_rec;
   w.rate_rec = rate_rec;
+  if (fused)
+    return f.finish(ey_nuts_mfma_launch(pl, theta, target, grad, metric, G, metric_index, step, step_vec, d, nu, w), theta);
   if (tree_ws)
     return f.finish(ey_nuts_ws_launch(pl, theta, target, grad, metric, G, metric_index, step, step_vec, d, nu, w), theta);
   return f.finish(ey_nuts_launch(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, d, nu, w), theta);
@@ -1309,6 +1320,13 @@ int ey_nuts_warmup(ey_plan* pl, void* theta, void* target, void* grad, const voi
                      (int*)depth_rec, (unsigned char*)divergent_rec};
   return nuts_impl(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, dr, nu, da_state, da_table, da_n,
                    d, log_eub, final_avg, mean, M2, count, steps_rec, rate_rec, "ey_nuts_warmup");
+}
+
+// (declared in include/eeyore_amd_nuts_fused.h)
+const char* ey_nuts_kernel(const ey_plan* pl, uint32_t flags) {
+  if (!pl || is_mix(pl)) return "generic";
+  EyVariantScope vs(pl);
+  return (flags & EY_NUTS_FUSED) && !(flags & EY_FORCE_GENERIC) && use_mfma32(pl) ? "mfma32" : "generic";
 }
 
 // (declared in include/eeyore_amd_eslice.h)

@@ -1,8 +1,8 @@
-// What ey_api.hip, ey_nuts.hip and ey_nuts_ws.hip share about the No-U-Turn sampler (include/eeyore_amd_nuts.h,
-// include/eeyore_amd_nuts_tree.h).
+// What ey_api.hip, ey_nuts.hip, ey_nuts_ws.hip and ey_nuts_mfma.hip share about the No-U-Turn sampler
+// (include/eeyore_amd_nuts.h, include/eeyore_amd_nuts_tree.h, include/eeyore_amd_nuts_fused.h).
 #pragma once
 
-#include "../../include/eeyore_amd_nuts_tree.h"  // includes eeyore_amd_nuts.h and the other five
+#include "../../include/eeyore_amd_nuts_fused.h"  // includes eeyore_amd_nuts_tree.h, eeyore_amd_nuts.h and the other six
 #include "ey_common.h"
 
 // the arguments of k_nuts beside those of ey_generic_hmc_metric_warmup: parity inputs, the depth cap, the outputs of a draw
@@ -31,6 +31,12 @@ int64_t ey_nuts_ws_bytes(const ey_plan* pl, int64_t C, int max_depth);
 int ey_nuts_ws_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int64_t G,
                       const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
                       const EyWarm& w);
+
+// k_nuts_mfma (ey_nuts_mfma.hip): the same draw on the matrix cores for the plans the mfma32 family serves, the tree in the
+// same workspace and layout.  The caller has checked the family, the form and the workspace.
+int ey_nuts_mfma_launch(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int64_t G,
+                        const void* metric_index, double step, void* step_vec, const EyDraw& d, const EyNuts& nu,
+                        const EyWarm& w);
 
 // The launch of one wave per chain.  The LDS limit of an instantiation is raised once per plan, to the whole 160 KiB
 // (DESIGN.md 4.9.1): the limit belongs to the kernel, not to a launch, and `attr` is the plan's slot for the kernel that has

@@ -695,12 +695,18 @@ class Plan:
         L.check(L.lib().ey_plan_attach_nuts_tree(self.handle, None, 0), "ey_plan_attach_nuts_tree")
         self._nuts_tree = None
 
+    def nuts_kernel(self, flags=0):
+        """'mfma32' or 'generic' (ey_nuts_kernel, include/eeyore_amd_nuts_fused.h): the kernel ``nuts_step``, ``nuts_run``
+        and ``nuts_warmup`` take on this plan under ``flags`` -- the draw on the matrix cores when
+        ``flags`` holds EY_NUTS_FUSED without EY_FORCE_GENERIC and ``kernel`` is 'mfma32', otherwise the generic kernels."""
+        return L.lib().ey_nuts_kernel(self.handle, int(flags)).decode()
+
     def _nuts_args(self, theta, metric, form, index, max_depth, out, flags=0):
         """(C, form code, G, index, out) of a NUTS call, checked: the metric as ``_metric`` checks it, at most 128 parameters
-        in either form -- unless ``flags`` carry EY_NUTS_TREE_DEVICE and the form is 'diag' (the tree in the attached
-        workspace) --, ``max_depth`` in [1, 10]; ``out`` gets the [C] outputs of a draw it does not hold yet."""
+        in either form -- unless ``flags`` carry EY_NUTS_TREE_DEVICE or EY_NUTS_FUSED and the form is 'diag' (the tree in
+        the attached workspace) --, ``max_depth`` in [1, 10]; ``out`` gets the [C] outputs of a draw it does not hold yet."""
         C = self._theta(theta)
-        if self.P > 128 and not (int(flags) & L.EY_NUTS_TREE_DEVICE and form == "diag"):
+        if self.P > 128 and not (int(flags) & (L.EY_NUTS_TREE_DEVICE | L.EY_NUTS_FUSED) and form == "diag"):
             raise ValueError(f"NUTS is limited to 128 parameters (the model has {self.P}): the tree lives in LDS")
         code, G, index = self._metric(metric, form, index, C)
         if int(max_depth) != max_depth:
@@ -722,7 +728,9 @@ class Plan:
         """One draw of multinomial NUTS for every chain under a fixed metric (ey_nuts_step): ``metric``,
         ``form`` and ``index`` as in ``hmc_metric_step``, at most 128 parameters in either form; ``max_depth`` in [1, 10]
         doublings.  With EY_NUTS_TREE_DEVICE in ``flags`` and form 'diag' the tree lives in the workspace of
-        ``attach_nuts_tree`` and P is not limited (include/eeyore_amd_nuts_tree.h; the same holds of the run and the warm-up).  ``v0`` [C, P] replaces the draw of the whitened velocity, ``u`` [C, S] (S >= 21 + 2^max_depth) the
+        ``attach_nuts_tree`` and P is not limited (include/eeyore_amd_nuts_tree.h; the same holds of the run and the warm-up);
+        with EY_NUTS_FUSED the draw also runs on the matrix cores where ``nuts_kernel`` says 'mfma32'
+        (include/eeyore_amd_nuts_fused.h).  ``v0`` [C, P] replaces the draw of the whitened velocity, ``u`` [C, S] (S >= 21 + 2^max_depth) the
         chain's uniform stream in its word layout (1 + 2d the direction of doubling d, 2 + 2d its top-level move, 21 + n
         leaf n).  Returns accepted (the state moved), depth, n_leapfrog, divergent, accept_stat, energy, each [C]."""
         C, code, G, index, out = self._nuts_args(theta, metric, form, index, max_depth, out, flags)

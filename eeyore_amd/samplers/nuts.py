@@ -6,7 +6,7 @@ from .metric import DenseMetric, DiagMetric
 from eeyore_amd.tuners import HMCDATuner, PerChainDATuner
 from eeyore_amd import _lib as L
 
-NUTS_MAX_P = 128  # ey_nuts_step keeps the tree's vectors in LDS, in either metric form, unless tree='device'
+NUTS_MAX_P = 128  # ey_nuts_step keeps the tree's vectors in LDS, in either metric form, unless tree='device' or 'fused'
 
 
 class NUTS(HMC):
@@ -24,6 +24,10 @@ class NUTS(HMC):
     (``metric=None``, 'diag' or a ``DiagMetric``; a dense one raises ``ValueError``).  The workspace, (12 + 2 max_depth)
     vectors per chain, is attached to the plan a launch is about to run on and grows with the largest call.
 
+    ``tree='fused'`` is ``tree='device'`` with every leapfrog step on the matrix cores (include/eeyore_amd_nuts_fused.h,
+    DESIGN.md 4.28): for the f32 MLP(4-32-32-dK) plans whose ``plan.kernel`` is 'mfma32', under the same diagonal metrics and
+    in the same workspace; a launch on any other plan raises ``ValueError`` naming ``plan.kernel``.
+
     ``theta0`` [C, P] or [P]; ``rng='torch'`` draws the velocity and the draw's table of uniforms on the host (the word
     layout of include/eeyore_amd_nuts.h), ``rng='philox'`` uses the in-kernel streams.  ``PerChainDATuner`` / ``HMCDATuner``
     adapt the step draw by draw on the draw's mean accept statistic; ``tuner=WindowedAdaptation(...)`` runs the whole
@@ -36,8 +40,8 @@ class NUTS(HMC):
     def __init__(self, model, theta0=None, dataloader=None, data0=None, counter=None, step=0.1, max_depth=10, metric=None,
                  tuner=None, chain=None, rng=None, seed=0, chain_offset=0, recompute_initial_grad=False, temperature=None,
                  init_step_mode='intended', tree='lds'):
-        if tree not in ('lds', 'device'):
-            raise ValueError("NUTS: tree must be 'lds' or 'device'")
+        if tree not in ('lds', 'device', 'fused'):
+            raise ValueError("NUTS: tree must be 'lds' or 'device', or 'fused' for the plans of the mfma32 family")
         if init_step_mode == 'reference':
             raise ValueError("NUTS: init_step_mode='reference' restates the reference's identity-mass heuristic and has no "
                              "metric form; use 'intended'")
@@ -47,8 +51,8 @@ class NUTS(HMC):
         if tree == 'lds' and P > NUTS_MAX_P:
             raise ValueError(f"NUTS is limited to {NUTS_MAX_P} parameters (the model has {P}): the tree lives in LDS; "
                              "pass tree='device' for a diagonal metric")
-        if tree == 'device' and (metric == 'dense' or isinstance(metric, DenseMetric)):
-            raise ValueError("NUTS: tree='device' serves a diagonal metric only (metric=None, 'diag' or a DiagMetric)")
+        if tree != 'lds' and (metric == 'dense' or isinstance(metric, DenseMetric)):
+            raise ValueError(f"NUTS: tree='{tree}' serves a diagonal metric only (metric=None, 'diag' or a DiagMetric)")
         self.tree = tree
         if metric is None:
             metric = DiagMetric.identity(P, dtype=model.dtype, device=model.device)
@@ -63,16 +67,23 @@ class NUTS(HMC):
         raise ValueError("NUTS.leapfrog: a NUTS trajectory has no fixed length; use HMC.leapfrog")
 
     def _set_metric(self, metric, index=None):
-        if getattr(self, 'tree', 'lds') == 'device' and isinstance(metric, DenseMetric):
-            raise ValueError("NUTS: tree='device' serves a diagonal metric only")
+        if getattr(self, 'tree', 'lds') != 'lds' and isinstance(metric, DenseMetric):
+            raise ValueError(f"NUTS: tree='{self.tree}' serves a diagonal metric only")
         super()._set_metric(metric, index)
 
     def _flags(self, plan):
-        """The flags of a launch on ``plan``; with tree='device' the plan first gets a workspace for this sampler's tree."""
+        """The flags of a launch on ``plan``; with tree='device' or 'fused' the plan first gets a workspace for this
+        sampler's tree."""
         flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
         if self.tree == 'device':
             plan.attach_nuts_tree(self.num_chains, self.max_depth)
             flags |= L.EY_NUTS_TREE_DEVICE
+        elif self.tree == 'fused':
+            if plan.nuts_kernel(L.EY_NUTS_FUSED) != 'mfma32':
+                raise ValueError(f"NUTS: tree='fused' serves the plans of the mfma32 family; this plan's kernel "
+                                 f"(plan.kernel) is '{plan.kernel}'; use tree='device'")
+            plan.attach_nuts_tree(self.num_chains, self.max_depth)
+            flags |= L.EY_NUTS_FUSED
         return flags
 
     # -- one draw

@@ -8,7 +8,12 @@ fit LDS beside the evaluation, so ``tree='device'`` keeps it in a workspace in d
 itself stays in LDS, one wave per chain.  The script prints the adapted steps, the tree depths of the stored draws, the
 divergent draws and the acceptance.  The chains start from draws of the prior scaled down.  EEYORE_EXAMPLE_CHAINS /
 EEYORE_EXAMPLE_EPOCHS shrink the run.
+
+``--tree fused`` runs the same sampler with every leapfrog step on the matrix cores (``NUTS(tree='fused')``):
+the same draw and the same workspace, for the plans whose ``plan.kernel`` is 'mfma32' -- this one is.  The default is
+``--tree device``.
 """
+import argparse
 import os
 import sys
 import time
@@ -30,6 +35,10 @@ MAX_DEPTH = 7
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument('--tree', choices=['device', 'fused'], default='device',
+                    help="where a leaf is evaluated: the generic kernel (device) or the matrix cores (fused)")
+    args = ap.parse_args()
     num_chains = int(os.environ.get('EEYORE_EXAMPLE_CHAINS', 1024))
     epochs = int(os.environ.get('EEYORE_EXAMPLE_EPOCHS', 200))
     warmup = max(20, epochs // 2)
@@ -44,7 +53,7 @@ def main():
 
     torch.manual_seed(1)
     tuner = WindowedAdaptation(num_steps=1)  # (the tuner's num_steps is not used by NUTS)
-    sampler = NUTS(model, theta0=0.1 * model.prior.sample((num_chains,)), dataloader=loader, tree='device', metric='diag',
+    sampler = NUTS(model, theta0=0.1 * model.prior.sample((num_chains,)), dataloader=loader, tree=args.tree, metric='diag',
                    max_depth=MAX_DEPTH, tuner=tuner, seed=1,
                    chain=ChainBuffer(keys=['sample', 'target_val', 'accepted', 'depth', 'divergent']))
     t0 = time.perf_counter()
@@ -56,6 +65,7 @@ def main():
     depth = chain.bufs['depth'][:len(chain)]
     div = chain.bufs['divergent'][:len(chain)]
     ends = ", ".join(str(h['draw']) for h in tuner.history) or "none"
+    print(f"tree='{args.tree}': NUTS runs on the {plan.nuts_kernel(sampler._flags(plan))} kernel")
     print(f"{num_chains} chains, {P} parameters, {warmup} warm-up draws and {epochs} stored: {seconds:.2f} s; the tree's "
           f"workspace holds {plan.nuts_tree_bytes(num_chains, MAX_DEPTH) / 2 ** 20:.1f} MiB")
     print(f"windowed warm-up: the metric re-estimated after draws {ends}; steps {sampler.step.min().item():.4f} ... "
