@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI HIP library (include/eeyore_amd.h, include/eeyore_amd_ext.h, include/eeyore_amd_warmup.h,
 include/eeyore_amd_nuts.h, include/eeyore_amd_eslice.h, include/eeyore_amd_eslice_fused.h,
-include/eeyore_amd_nuts_tree.h, include/eeyore_amd_nuts_fused.h).
+include/eeyore_amd_nuts_tree.h, include/eeyore_amd_nuts_fused.h, include/eeyore_amd_hmc_metric_fused.h).
 
 The library is the product path: there is no CPU or eager fallback.  ``lib()`` raises if the shared
 object is missing, and every compute call raises ``RuntimeError`` with ``ey_last_error()`` on failure.
@@ -160,6 +160,15 @@ NUTS_FUSED_SYMBOLS = {
     "ey_nuts_kernel": (ct.c_char_p, [_vp, _u32]),
 }
 
+# ... and what include/eeyore_amd_hmc_metric_fused.h declares, a ninth table: HMC under a diagonal metric and its warm-up on
+# the matrix cores for the plans of the mfma32 family.  EY_HMC_METRIC_FUSED is a bit of the flags of ey_hmc_metric_step /
+# ey_hmc_metric_run / ey_hmc_metric_warmup; ey_hmc_metric_kernel says which kernel serves a plan under given flags,
+# b"mfma32" or b"generic".
+EY_HMC_METRIC_FUSED = 32
+HMC_METRIC_FUSED_SYMBOLS = {
+    "ey_hmc_metric_kernel": (ct.c_char_p, [_vp, _u32]),
+}
+
 
 def build(force=False, verbose=False, diagnostics=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  ``diagnostics``: also the fused16
@@ -193,7 +202,7 @@ def lib():
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(WARMUP_SYMBOLS.items())
                                   + list(NUTS_SYMBOLS.items()) + list(ESLICE_SYMBOLS.items())
                                   + list(ESLICE_FUSED_SYMBOLS.items()) + list(NUTS_TREE_SYMBOLS.items())
-                                  + list(NUTS_FUSED_SYMBOLS.items())):
+                                  + list(NUTS_FUSED_SYMBOLS.items()) + list(HMC_METRIC_FUSED_SYMBOLS.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -10,6 +10,7 @@
 #include "ey_common.h"
 #include "ey_nuts.h"
 #include "ey_eslice.h"
+#include "ey_hmc_metric_mfma.h"
 
 static thread_local std::string g_err;
 void ey_set_error(const std::string& msg) { g_err = msg; }
@@ -957,7 +958,21 @@ static int mala_tril_impl(ey_plan* pl, void* theta, void* target, void* grad, co
   return f.finish(ey_generic_mala_tril(pl, theta, target, grad, tril, G, tril_index, z, u, step, step_vec, d), theta);
 }
 
-// HMC with a fixed metric: one kernel of ey_generic.hip for every model, as the samplers with a factor above.  An attached
+// EY_HMC_METRIC_FUSED (include/eeyore_amd_hmc_metric_fused.h): what a call with the bit is refused for, after every refusal
+// of a call without it and before ready().  `fused` says whether the call runs on k_hmc_metric_mfma.
+static int hmc_metric_fused(EyCall& f, const ey_plan* pl, int form, uint32_t flags, const char* who, bool& fused) {
+  fused = (flags & EY_HMC_METRIC_FUSED) != 0;
+  if (!fused) return EY_OK;
+  if (form != EY_METRIC_DIAG) return f.refuse("EY_HMC_METRIC_FUSED: diagonal metric only (form EY_METRIC_DIAG)");
+  if (flags & EY_FORCE_GENERIC) return f.refuse("EY_HMC_METRIC_FUSED and EY_FORCE_GENERIC contradict each other");
+  if (is_mix(pl) || !use_mfma32(pl))
+    EY_FAIL(EY_ERR_UNSUPPORTED, std::string(who) + ": EY_HMC_METRIC_FUSED serves the plans of the mfma32 family with the "
+                                "batch they hold; this plan's kernel (ey_plan_kernel) is \"" + ey_plan_kernel(pl) + "\"");
+  return EY_OK;
+}
+
+// HMC with a fixed metric: one kernel of ey_generic.hip for every model, as the samplers with a factor above -- and, with
+// EY_HMC_METRIC_FUSED, k_hmc_metric_mfma for the plans of the mfma32 family.  An attached
 // dual averaging is refused, not ignored: this kernel does not consume the table, and hmc_impl's callers rely on it.
 static int hmc_metric_impl(ey_plan* pl, void* theta, void* target, void* grad, const void* metric, int form, int64_t G,
                            const void* metric_index, const void* v0, const void* u, double step, const void* step_vec,
@@ -974,7 +989,12 @@ static int hmc_metric_impl(ey_plan* pl, void* theta, void* target, void* grad, c
   if (pl->da_state)
     return f.refuse("a dual-averaging table is attached (ey_plan_attach_da), which HMC with a metric does not consume; "
                     "detach it and adapt on the host");
+  bool fused;
+  EY_TRY(hmc_metric_fused(f, pl, form, d.flags, who, fused));
   EY_TRY(f.ready(true));
+  if (fused)
+    return f.finish(ey_hmc_metric_mfma_launch(pl, theta, target, grad, metric, G, metric_index, v0, u, step,
+                                              const_cast<void*>(step_vec), L, d, rate, hcur, hprop, EyWarm{}), theta);
   return f.finish(ey_generic_hmc_metric(pl, theta, target, grad, metric, form, G, metric_index, v0, u, step, step_vec, L,
                                         d, rate, hcur, hprop), theta);
 }
@@ -1264,6 +1284,8 @@ int ey_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, con
   if (da_state && !std::isfinite(d)) return f.refuse("the target acceptance d must be finite");
   if (!mean != !M2) return f.refuse("mean and M2 go together: exactly one of them is null");
   if (mean && count < 0) return f.refuse("count must be >= 0");
+  bool fused;
+  EY_TRY(hmc_metric_fused(f, pl, form, flags, "ey_hmc_metric_warmup", fused));
   EY_TRY(f.ready(true));
   EyWarm w;
   w.da_state = (double*)da_state;
@@ -1278,6 +1300,9 @@ int ey_hmc_metric_warmup(ey_plan* pl, void* theta, void* target, void* grad, con
   w.count = count;
   w.steps_rec = steps_rec;
   w.rate_rec = rate_rec;
+  if (fused)
+    return f.finish(ey_hmc_metric_mfma_launch(pl, theta, target, grad, metric, G, metric_index, nullptr, nullptr, step,
+                                              step_vec, L, dr, nullptr, nullptr, nullptr, w), theta);
   return f.finish(ey_generic_hmc_metric_warmup(pl, theta, target, grad, metric, form, G, metric_index, step, step_vec, L,
                                                dr, w), theta);
 }
@@ -1327,6 +1352,13 @@ const char* ey_nuts_kernel(const ey_plan* pl, uint32_t flags) {
   if (!pl || is_mix(pl)) return "generic";
   EyVariantScope vs(pl);
   return (flags & EY_NUTS_FUSED) && !(flags & EY_FORCE_GENERIC) && use_mfma32(pl) ? "mfma32" : "generic";
+}
+
+// (declared in include/eeyore_amd_hmc_metric_fused.h)
+const char* ey_hmc_metric_kernel(const ey_plan* pl, uint32_t flags) {
+  if (!pl || is_mix(pl)) return "generic";
+  EyVariantScope vs(pl);
+  return (flags & EY_HMC_METRIC_FUSED) && !(flags & EY_FORCE_GENERIC) && use_mfma32(pl) ? "mfma32" : "generic";
 }
 
 // (declared in include/eeyore_amd_eslice.h)

@@ -601,6 +601,13 @@ class Plan:
             return L.EY_METRIC_DIAG, G, None
         return L.EY_METRIC_DIAG, G, self._index(index, G, C)
 
+    def hmc_metric_kernel(self, flags=0):
+        """'mfma32' or 'generic' (ey_hmc_metric_kernel, include/eeyore_amd_hmc_metric_fused.h): the kernel
+        ``hmc_metric_step``, ``hmc_metric_run`` and ``hmc_metric_warmup`` take on this plan under a diagonal metric with
+        ``flags`` -- the draw on the matrix cores when ``flags`` holds EY_HMC_METRIC_FUSED without
+        EY_FORCE_GENERIC and ``kernel`` is 'mfma32', otherwise the generic kernels."""
+        return L.lib().ey_hmc_metric_kernel(self.handle, int(flags)).decode()
+
     def hmc_metric_step(self, theta, target, grad, step, num_steps, metric, form, index=None, v0=None, u=None,
                         step_vec=None, temp=None, seed=0, it=0, chain_offset=0, flags=0, out=None):
         """One HMC draw of every chain under a fixed metric with inverse L L^T (ey_hmc_metric_step,

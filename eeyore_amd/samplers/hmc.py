@@ -35,14 +35,26 @@ class HMC(SingleChainSerialSampler):
     stored or read back between draws.  ``metric`` is the starting metric and its form the form adapted; 'diag' / 'dense'
     are shorthands for the identity of that form.  After burn-in ``metric`` is the adapted ``DiagMetric`` / ``DenseMetric``,
     ``step`` the [C] averaged steps, and the run goes on as any run under a fixed metric.  It needs C chains on the in-kernel
-    streams with a full batch: ``ValueError`` otherwise, saying which condition failed."""
+    streams with a full batch: ``ValueError`` otherwise, saying which condition failed.
+
+    ``metric_kernel='fused'`` (default 'generic': nothing changes) runs every call the sampler makes under a diagonal metric
+    -- ``draw``, the blocks of ``run``, ``init_step`` / ``init_step_per_chain`` and the whole ``WindowedAdaptation`` warm-up --
+    on the matrix cores (EY_HMC_METRIC_FUSED, include/eeyore_amd_hmc_metric_fused.h): for the f32
+    MLP(4-32-32-dK) plans whose ``plan.kernel`` is 'mfma32', with ``metric`` a ``DiagMetric`` or 'diag'.  Without a metric or
+    with a dense one the constructor raises ``ValueError``; a launch on any other plan raises ``ValueError`` naming
+    ``plan.kernel``."""
 
     keys = ['sample', 'target_val', 'grad_val', 'momentum', 'hamiltonian', 'accepted']
 
     def __init__(self, model, theta0=None, dataloader=None, data0=None, counter=None, step=0.1, num_steps=10,
                  tuner=None, chain=None, rng=None, seed=0, chain_offset=0, recompute_initial_grad=False,
-                 temperature=None, init_step_mode='intended', metric=None):
+                 temperature=None, init_step_mode='intended', metric=None, metric_kernel='generic'):
         super().__init__(default_counter(counter, dataloader))
+        if metric_kernel not in ('generic', 'fused'):
+            raise ValueError("HMC: metric_kernel must be 'generic' or 'fused'")
+        if metric_kernel == 'fused' and not (metric == 'diag' if isinstance(metric, str) else isinstance(metric, DiagMetric)):
+            raise ValueError("HMC: metric_kernel='fused' serves a diagonal metric only (metric='diag' or a DiagMetric)")
+        self.metric_kernel = metric_kernel
         self._configure(model, dataloader, theta0, chain, rng, seed, chain_offset, temperature)
         if init_step_mode not in ('intended', 'reference'):
             raise ValueError("init_step_mode must be 'intended' or 'reference'")
@@ -109,6 +121,8 @@ class HMC(SingleChainSerialSampler):
         """Take a ``DiagMetric`` / ``DenseMetric`` (or None: identity mass, the plain kernels) to the device, checked:
         one entry for all chains, one per chain, or a table of G entries with ``index`` (int32 [C]) naming the entry of
         every chain."""
+        if getattr(self, 'metric_kernel', 'generic') == 'fused' and not isinstance(metric, DiagMetric):
+            raise ValueError("HMC: metric_kernel='fused' serves a diagonal metric only")
         self.metric = metric
         self._metric = self._metric_form = self._metric_index = None
         if metric is None:
@@ -128,6 +142,16 @@ class HMC(SingleChainSerialSampler):
         self._metric_form = metric.form
         if index is not None:
             self._metric_index = torch.as_tensor(index).to(device=self.model.device, dtype=torch.int32).contiguous()
+
+    def _metric_flags(self, plan):
+        """The bits a call under the metric adds to its flags on ``plan``: EY_HMC_METRIC_FUSED with metric_kernel='fused',
+        once the plan has said that the fused kernel serves it."""
+        if getattr(self, 'metric_kernel', 'generic') != 'fused':
+            return 0
+        if plan.hmc_metric_kernel(L.EY_HMC_METRIC_FUSED) != 'mfma32':
+            raise ValueError(f"HMC: metric_kernel='fused' serves the plans of the mfma32 family; this plan's kernel "
+                             f"(plan.kernel) is '{plan.kernel}'; use metric_kernel='generic'")
+        return L.EY_HMC_METRIC_FUSED
 
     def _metric_of(self, c):
         """Chain c's own entry of the metric table, as a table of one."""
@@ -178,7 +202,8 @@ class HMC(SingleChainSerialSampler):
 
             def ratio_after_one_step():
                 out = plan.hmc_metric_step(th1.clone(), t1.clone(), g1.clone(), self.step, 1, m0, self._metric_form,
-                                           v0=momentum[None].contiguous(), u=half, temp=temp)
+                                           v0=momentum[None].contiguous(), u=half, temp=temp,
+                                           flags=self._metric_flags(plan))
                 return torch.exp(out['h_cur'] - out['h_prop']).item()
         else:
             h_start = self.hamiltonian(-self.model.log_target(th.clone(), x, y), momentum)
@@ -224,7 +249,7 @@ class HMC(SingleChainSerialSampler):
             if self._metric is not None:  # one leapfrog step of ey_hmc_metric_step on cloned state, v0 = momentum
                 out = plan.hmc_metric_step(th0.clone(), t0.clone(), g0.clone(), 0.0, 1, self._metric, self._metric_form,
                                            index=self._metric_index, v0=momentum, u=torch.full_like(step, 0.5),
-                                           step_vec=step, temp=self._temp())
+                                           step_vec=step, temp=self._temp(), flags=self._metric_flags(plan))
                 return torch.exp(out['h_cur'] - out['h_prop'])
             th, p = th0.clone(), momentum.clone()
             t, _ = plan.leapfrog(th, p, 0.0, 1, step_vec=step, temp=self._temp())
@@ -300,6 +325,7 @@ class HMC(SingleChainSerialSampler):
         step, step_vec = self._step_args()
         flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
         if self._metric is not None:
+            flags |= self._metric_flags(plan)
             out = plan.hmc_metric_run(self._theta, self._target, self._grad, step, self.num_steps, self._metric,
                                       self._metric_form, k, index=self._metric_index, step_vec=step_vec, temp=self._temp(),
                                       seed=self.seed, it=self._iter, chain_offset=self.chain_offset, flags=flags, **rec)
@@ -322,6 +348,7 @@ class HMC(SingleChainSerialSampler):
         step, step_vec = self._step_args()
         flags = L.EY_RECOMPUTE_INITIAL_GRAD if self.recompute_initial_grad else 0
         if self._metric is not None:  # p0 is then the whitened velocity v = L^T p
+            flags |= self._metric_flags(plan)
             out = plan.hmc_metric_step(self._theta, self._target, self._grad, step, self.num_steps, self._metric,
                                        self._metric_form, index=self._metric_index, v0=p0, u=u, temp=temp,
                                        step_vec=step_vec, seed=self.seed, it=self._iter, chain_offset=self.chain_offset,

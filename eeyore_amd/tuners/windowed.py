@@ -112,6 +112,7 @@ class WindowedAdaptation(Tuner):
         if plan._moments is not None:  # attached chain moments are replayed from records a burn-in block does not keep
             block = 1
         flags = L.EY_RECOMPUTE_INITIAL_GRAD if sampler.recompute_initial_grad else 0
+        flags |= sampler._metric_flags(plan)  # HMC(metric_kernel='fused'): EY_HMC_METRIC_FUSED; otherwise nothing
         # a sampler with a warm-up launch of its own (NUTS: ey_nuts_warmup) gives it as _warmup_launch(plan, num_steps, k,
         # **the keywords below); HMC has none and goes through ey_hmc_metric_warmup
         launch = getattr(sampler, '_warmup_launch', None)
